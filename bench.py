@@ -12,7 +12,10 @@ like grid_obj.f90:39-255 (BASELINE.json configs[2] is this grid as 2x2).  --scal
 instead (the global domain grows with the image grid).  One call per sub-step into the library (icar_hip_update_dt +
 icar_hip_substep): the launches, the second stream and the RCCL halo exchange are issued from C.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus "roofline" and "cpu_baseline".
+Prints ONE JSON line (rank 0) with the driver's contract and the configuration.  A plain run sets up, warms up, times the K steps
+(the library's event timers off), writes the last step's outputs with --dump-outputs DIR, and prints the line.  --full adds what
+the headline does not need: "roofline" and "microphysics" (event timers, a timer window after the timed one, a streaming-copy
+measurement, two rocprofv3 --pmc child runs), "later_window", "cpu_baseline" and "cpu_reference".
 """
 import argparse
 import ctypes
@@ -85,6 +88,8 @@ SETUP_KERNELS = ("k_setup_winds", "k_mpdata_coef")      # launched once per step
 KERNEL_GENERATION = "r06c: r05's branch-free paired steady steps + a donor-cell pass bit-identical to the reference (exact quotients from v_rcp + Newton); 11 coefficient arrays, the final update's reciprocals from the donor-cell pass (registers / LDS): 81 loads per step (k_mpdata_fused + k_mpdata_coef)"
 
 FORCED = [("water_vapor", True), ("potential_temperature", True), ("u", False), ("v", False), ("pressure", False), ("w", False)]
+# --dump-outputs: values per field at most (float32: 1 MB, float64: 2 MB); at most 22 fields, so a dump stays under 64 MB
+DUMP_SAMPLE = 1 << 18
 
 
 def run_steps(d, opt, n):
@@ -97,6 +102,65 @@ def run_steps(d, opt, n):
     rank of an N>1 run pays."""
     from icar_amd.time_step import step_n
     return step_n(d, n, opt, forced=FORCED)
+
+
+# The synthetic case is not a steady state: left to itself its potential temperature leaves the physical range after ~150 steps
+# and turns non-finite near step 360 (512x512x40, Thompson + MPDATA, measured on the MI355X).  So no state is stepped more than
+# SEGMENT steps past the initial one: the steps run in segments, and between two segments, outside any timed region, the advected
+# scalars and the model and microphysics clocks go back to the initial state (winds, pressure and the forcing stay as they are:
+# the zero tendencies leave them unchanged).  A run of at most SEGMENT steps (warm-up included) is one segment.
+SEGMENT = 300
+RESTORED = ["water_vapor", "cloud_water", "rain", "snow", "potential_temperature", "cloud_ice", "graupel", "ice_number", "rain_number"]
+
+
+class Stepper:
+    def __init__(self, d, opt, case, barrier):
+        self.d, self.opt, self.barrier = d, opt, barrier
+        self.initial = {k: case[k] for k in RESTORED if k in case}
+        self.since = 0                               # steps since the initial state
+
+    def restore(self):
+        from icar_amd.capi import lib, check
+        self.d.load_case(self.initial)
+        self.d.model_time_seconds = 0.0
+        check(lib().icar_hip_mp_reset(self.d.ctx), "icar_hip_mp_reset")
+        self.since = 0
+
+    def run(self, n):
+        """n steps (run_steps) in segments; returns (dt of the last step, seconds the steps took, barriers included)"""
+        dt, elapsed = None, 0.0
+        while n > 0:
+            if self.since >= SEGMENT:
+                self.restore()
+                self.barrier()
+            m = min(n, SEGMENT - self.since)
+            t0 = time.perf_counter()
+            dt = run_steps(self.d, self.opt, m)
+            self.barrier()
+            elapsed += time.perf_counter() - t0
+            n -= m; self.since += m
+        return dt, elapsed
+
+
+def dump_outputs(d, opt, dt, path):
+    """What the timed path leaves a caller after its last step, one DIR/<member>.npy each: the advected scalars, the forced winds
+    and pressure, the step's diagnostics, the accumulated precipitation of the microphysics, and dt.npy (the last step's dt).
+    A field of more than DUMP_SAMPLE values is cut to a fixed sample of its cells (np.random.default_rng(0) over the flattened
+    field, sorted): the same cells in every run with the same arguments, so that two builds compare output for output."""
+    from icar_amd.constants import ADVECTION_ORDER, KVARS
+    os.makedirs(path, exist_ok=True)
+    names = [KVARS[n][1] for n in ADVECTION_ORDER if opt.vars_to_advect.get(n, 0) > 0]
+    names += ["u", "v", "w", "pressure", "exner", "density", "temperature", "w_real"]
+    names += [KVARS[n][1] for n in ("precipitation", "snowfall", "graupel") if opt.vars_to_allocate.get(n, 0) > 0]
+    sample = {}                              # field size -> the sorted cell indices of its sample
+    for name in names:
+        a = d.get(name).ravel()
+        if a.size > DUMP_SAMPLE:
+            if a.size not in sample:
+                sample[a.size] = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a[sample[a.size]]
+        np.save(os.path.join(path, name + ".npy"), a)
+    np.save(os.path.join(path, "dt.npy"), np.array([dt], np.float64))
 
 
 def cpu_reference(args, nscalars):
@@ -249,6 +313,121 @@ def probe_traffic(args):
     return rd + wr, rd, wr, setup_bytes
 
 
+def full_figures(args, d, lib, world, rank, device, red_device, nscal, barrier, stepper):
+    """--full: what the line carries beyond the headline, measured after the timed region (every rank takes part in the windows
+    and reductions; rank 0 gets the dict, the others None): config.mp_active_column_fraction, later_window, roofline,
+    microphysics, cpu_baseline / cpu_reference."""
+    tot = ctypes.c_double(); n = ctypes.c_int()
+    lib.icar_hip_timing_read(d.ctx, b"advect", ctypes.byref(tot), ctypes.byref(n))
+    adv_ms = tot.value / max(n.value, 1)
+    diag_steps = max(1, min(args.steps, 10))
+    lib.icar_hip_timing_groups(d.ctx, b"mp,winds"); lib.icar_hip_timing_reset(d.ctx)
+    stepper.run(diag_steps)                  # untimed: the microphysics and advection-setup timers of the steps that follow
+
+    # roofline of the dominant kernel group: the MPDATA advection launches, HIP events on the ctx stream
+    lib.icar_hip_timing_read(d.ctx, b"mp", ctypes.byref(tot), ctypes.byref(n))
+    mp_ms_step = tot.value / diag_steps
+    lib.icar_hip_timing_read(d.ctx, b"winds", ctypes.byref(tot), ctypes.byref(n))     # k_setup_winds + k_mpdata_coef, beside the interior mp
+    winds_ms = tot.value / max(n.value, 1)
+    mem_cells = d.nx * d.ny * d.nz
+    alg_bytes = mem_cells * (8 * nscal + 16)            # SURVEY.md 8(d): B_adv = 8N+16 bytes per cell
+    achieved = alg_bytes / (adv_ms * 1e-3) / 1e9 if adv_ms > 0 else 0.0
+    # HBM bytes per advect() call from the PMC passes (profiles/run_profiles.sh: FETCH_SIZE x2 + WRITE_SIZE, separate
+    # runs of this same command): counters cannot be read inside this process, so the figure is attached only when it was
+    # taken on THIS configuration and THIS kernel generation; otherwise null.
+    traffic, traffic_source = None, None
+    tpath = os.path.join(ROOT, "profiles", "advect_traffic.json")
+    if os.path.exists(tpath):
+        try:
+            tj = json.load(open(tpath))
+            want = {"nx": d.nx, "ny": d.ny, "nz": d.nz, "adv": args.adv, "nscalars": nscal, "kernels": ADVECT_KERNELS[args.adv],
+                    "generation": KERNEL_GENERATION}
+            if tj.get("config") == want and not args.mpdata_exact:      # (the recorded passes are the fused kernel's)
+                traffic = tj.get("hbm_bytes_per_advect_call")
+                traffic_source = "profiles/advect_traffic.json (PMC passes of an earlier run of this configuration and kernel generation)"
+        except Exception:
+            traffic = None
+
+    stream_gbs = None
+    if rank == 0:
+        # SURVEY 8(d): the spec peak next to what a plain streaming copy sustains on THIS box (read + write of 1 GiB,
+        # torch's device-to-device copy kernel), measured outside the timed region
+        try:
+            a = torch.empty(1 << 28, dtype=torch.float32, device=device); b = torch.empty_like(a)
+            b.copy_(a); torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                b.copy_(a)
+            e1.record(); torch.cuda.synchronize()
+            stream_gbs = 5 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            del a, b
+        except Exception:  # pragma: no cover
+            stream_gbs = None
+
+    if rank == 0:
+        # liveness: how much of the tile the microphysics is doing work in
+        qc = d.get("cloud_water_mass"); qr = d.get("rain_mass")
+        active = float((((qc > 1e-8) | (qr > 1e-8)).any(axis=1)).mean())
+    # The cost of a step depends on the model state through the microphysics (the ideal case rains out): outside the timed region,
+    # the same K steps once more after 100 further steps, as a second window next to the headline one (informational).
+    later = None
+    if not args.no_later_window and not args.no_cpu_baseline:      # (like the traffic probe: not with --no-cpu-baseline)
+        stepper.run(100)
+        later_ms = stepper.run(args.steps)[1] / args.steps * 1e3
+        if world > 1:
+            t = torch.tensor([later_ms], dtype=torch.float64, device=red_device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            later_ms = float(t.item())
+        if rank == 0:
+            qc = d.get("cloud_water_mass"); qr = d.get("rain_mass")
+            later = {"after_steps": args.warmup + args.steps + diag_steps + 100, "steps": args.steps, "ms_per_step": later_ms,
+                     "mp_active_column_fraction": float((((qc > 1e-8) | (qr > 1e-8)).any(axis=1)).mean())}
+    if rank != 0:
+        return None
+    out = {
+        "mp_active_column_fraction": active,
+        "later_window": later,
+        "roofline": {"bound": "hbm", "kernel": "advect (k_upwind_pass + k_mpx_velocities + k_mpx_limit_donor: icar_hip_mpdata_exact)" if (args.mpdata_exact and args.adv == "mpdata")
+                                               else f"advect ({ADVECT_KERNELS[args.adv]})",
+                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                     "traffic": traffic, "traffic_source": traffic_source, "algorithmic_bytes": alg_bytes, "avg_ms": adv_ms,
+                     # mp_ms_per_step / setup_ms_per_step: over the `timer_window_steps` steps that FOLLOW the timed region (see above)
+                     "mp_ms_per_step": mp_ms_step, "timer_window_steps": diag_steps,
+                     # the once-per-step setup of the advection (Courant winds + the scalar-independent MPDATA coefficients),
+                     # issued beside the interior microphysics; not part of avg_ms
+                     "setup_ms_per_step": winds_ms,
+                     # the advection GROUP of a step = advect() + its setup kernels, whatever they run beside: same algorithmic
+                     # bytes (the setup reads nothing the 8N+16 model does not already count) over the sum of the two timers
+                     "group_ms": adv_ms + winds_ms,
+                     "frac_group": (alg_bytes / ((adv_ms + winds_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS) if adv_ms + winds_ms > 0 else None,
+                     # informational (SURVEY 8d): scalar-cell updates/s of the advection alone, and the measured
+                     # streaming-copy bandwidth of this box beside the spec peak that `frac` uses
+                     "advect_scalar_cell_updates_per_s": (mem_cells * nscal / (adv_ms * 1e-3)) if adv_ms > 0 else None,
+                     "measured_copy_GBps": stream_gbs,
+                     "frac_of_measured_copy": (achieved / stream_gbs) if stream_gbs else None},
+        # informational (SURVEY 8d): the microphysics is VALU-bound, its share of the step and its algorithmic traffic
+        "microphysics": {"kernel": {"thompson": "k_thompson_pack", "simple": "k_mp_simple_pack", "wsm3": "k_wsm3", "wsm6": "k_w6"}.get(args.mp, "none"), "bound": "valu",
+                         "ms_per_step": mp_ms_step,
+                         "algorithmic_GBps": (mem_cells * (84 if args.mp == "thompson" else 56) / (mp_ms_step * 1e-3) / 1e9) if mp_ms_step > 0 else 0.0},
+    }
+    if world == 1 and not args.no_traffic_probe and not args.no_cpu_baseline and not args.mpdata_exact:        # (profiling scripts pass --no-cpu-baseline)
+        # roofline.traffic measured NOW on this box (counters cannot be read inside this process: two child runs under rocprofv3)
+        t = probe_traffic(args)
+        if t is not None:
+            out["roofline"].update({"traffic": t[0], "traffic_read_bytes": t[1], "traffic_write_bytes": t[2],
+                                    "traffic_setup_bytes": t[3], "traffic_group": t[0] + t[3],
+                                    "traffic_group_over_algorithmic": (t[0] + t[3]) / alg_bytes,
+                                    "traffic_source": "live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, FETCH_SIZE x 2 for gfx950) over "
+                                                      "3-step child runs of this configuration, mean per dispatch of " + ADVECT_KERNELS[args.adv]})
+    if not args.no_cpu_baseline and world == 1:          # the CPU legs are timed at N=1 only (the other ranks would idle at the barrier)
+        out["cpu_baseline"] = cpu_baseline(args, nscal)
+        r = cpu_reference(args, nscal)
+        if r is not None:
+            out["cpu_reference"] = r
+    return out
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: re-run this command line as N ranks (one per GPU, RCCL) under
     torch.distributed.run on 127.0.0.1 and pass rank 0's JSON line through."""
@@ -274,13 +453,20 @@ def main():
     ap.add_argument("--mp", default=os.environ.get("ICAR_BENCH_MP", "thompson"), choices=["thompson", "simple", "wsm3", "wsm6", "none"])
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="strong (default): the nx x ny x nz grid is global and split over the GPUs; weak: it is the tile of every GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-later-window", action="store_true", help="skip the second (untimed-region) window 100 steps later")
-    ap.add_argument("--no-traffic-probe", action="store_true", help="skip the two rocprofv3 --pmc child runs that measure roofline.traffic")
-    ap.add_argument("--no-kernel-timers", action="store_true", help="profiling: leave the library's per-group HIP-event timers off (roofline.avg_ms is then 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and microphysics timers, later window, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs, the later window and the traffic probe")
+    ap.add_argument("--no-later-window", action="store_true", help="with --full: skip the second (untimed-region) window 100 steps later")
+    ap.add_argument("--no-traffic-probe", action="store_true", help="with --full: skip the two rocprofv3 --pmc child runs that measure roofline.traffic")
+    ap.add_argument("--no-kernel-timers", action="store_true", help="with --full: leave the library's per-group HIP-event timers off (roofline.avg_ms is then 0)")
     ap.add_argument("--mpdata-exact", action="store_true",
                     help="advect with icar_hip_mpdata_exact(ctx, 1): MPDATA in the reference's operation order, bit-identical to the CPU reference")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what their last step computed as DIR/<name>.npy (rank 0's tile; fields of more "
+                         f"than {DUMP_SAMPLE} values as a fixed, seeded sample of them)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)
@@ -346,25 +532,20 @@ def main():
             d.close()
             raise SystemExit(3)
 
+    stepper = Stepper(d, opt, case, barrier)
     if args.warmup > 0:
-        run_steps(d, opt, args.warmup)
+        stepper.run(args.warmup)
     barrier()
-    # Inside the timed region only the advection is bracketed by HIP events (roofline.avg_ms: two timestamped packets per step on
-    # the stream it is launched on); the other groups' timers cost ~5 us each and a sub-step has a dozen of them (0.06 ms per step:
-    # 2 % of this grid's step, 10 % of its 8-GPU tile's), so they run in a diagnostic window of their own after the timed one.
-    lib.icar_hip_timing_groups(d.ctx, b"advect")
-    lib.icar_hip_timing_enable(d.ctx, 0 if args.no_kernel_timers else 1); lib.icar_hip_timing_reset(d.ctx)
-    t0 = time.perf_counter()
-    dt = run_steps(d, opt, args.steps)       # exactly K steps: K x (icar_hip_update_dt + icar_hip_substep), issued from C
-    barrier()
-    elapsed = time.perf_counter() - t0
-    tot = ctypes.c_double(); n = ctypes.c_int()
-    lib.icar_hip_timing_read(d.ctx, b"advect", ctypes.byref(tot), ctypes.byref(n))
-    adv_ms = tot.value / max(n.value, 1)
-    diag_steps = max(1, min(args.steps, 10))
-    lib.icar_hip_timing_groups(d.ctx, b"mp,winds"); lib.icar_hip_timing_reset(d.ctx)
-    run_steps(d, opt, diag_steps)            # untimed: the microphysics and advection-setup timers of the steps that follow
-    barrier()
+    # A plain run leaves the library's event timers off.  With --full, inside the timed region only the advection is bracketed by
+    # HIP events (roofline.avg_ms: two timestamped packets per step on the stream it is launched on); the other groups' timers cost
+    # ~5 us each and a sub-step has a dozen of them (0.06 ms per step: 2 % of this grid's step, 10 % of its 8-GPU tile's), so they
+    # run in a diagnostic window of their own after the timed one.
+    if args.full:
+        lib.icar_hip_timing_groups(d.ctx, b"advect")
+    lib.icar_hip_timing_enable(d.ctx, 1 if args.full and not args.no_kernel_timers else 0); lib.icar_hip_timing_reset(d.ctx)
+    dt, elapsed = stepper.run(args.steps)    # exactly K steps: K x (icar_hip_update_dt + icar_hip_substep), issued from C
+    if args.dump_outputs and rank == 0:
+        dump_outputs(d, opt, dt, args.dump_outputs)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -376,69 +557,6 @@ def main():
         dist.all_reduce(cells_t)
     total_cells = float(cells_t.item())
 
-    # roofline of the dominant kernel group: the MPDATA advection launches, HIP events on the ctx stream
-    lib.icar_hip_timing_read(d.ctx, b"mp", ctypes.byref(tot), ctypes.byref(n))
-    mp_ms_step = tot.value / diag_steps
-    lib.icar_hip_timing_read(d.ctx, b"winds", ctypes.byref(tot), ctypes.byref(n))     # k_setup_winds + k_mpdata_coef, beside the interior mp
-    winds_ms = tot.value / max(n.value, 1)
-    mem_cells = d.nx * d.ny * d.nz
-    alg_bytes = mem_cells * (8 * nscal + 16)            # B_adv = 8N+16 bytes per cell
-    achieved = alg_bytes / (adv_ms * 1e-3) / 1e9 if adv_ms > 0 else 0.0
-    # HBM bytes per advect() call from the PMC passes (profiles/run_profiles.sh: FETCH_SIZE x2 + WRITE_SIZE, separate
-    # runs of this same command): counters cannot be read inside this process, so the figure is attached only when it was
-    # taken on THIS configuration and THIS kernel generation; otherwise null.
-    traffic, traffic_source = None, None
-    tpath = os.path.join(ROOT, "profiles", "advect_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            want = {"nx": d.nx, "ny": d.ny, "nz": d.nz, "adv": args.adv, "nscalars": nscal, "kernels": ADVECT_KERNELS[args.adv],
-                    "generation": KERNEL_GENERATION}
-            if tj.get("config") == want and not args.mpdata_exact:      # (the recorded passes are the fused kernel's)
-                traffic = tj.get("hbm_bytes_per_advect_call")
-                traffic_source = "profiles/advect_traffic.json (PMC passes of an earlier run of this configuration and kernel generation)"
-        except Exception:
-            traffic = None
-
-    stream_gbs = None
-    if rank == 0:
-        # the spec peak next to what a plain streaming copy sustains on THIS box (read + write of 1 GiB,
-        # torch's device-to-device copy kernel), measured outside the timed region
-        try:
-            a = torch.empty(1 << 28, dtype=torch.float32, device=device); b = torch.empty_like(a)
-            b.copy_(a); torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(5):
-                b.copy_(a)
-            e1.record(); torch.cuda.synchronize()
-            stream_gbs = 5 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-            del a, b
-        except Exception:  # pragma: no cover
-            stream_gbs = None
-
-    if rank == 0:
-        # liveness: how much of the tile the microphysics is doing work in
-        qc = d.get("cloud_water_mass"); qr = d.get("rain_mass")
-        active = float((((qc > 1e-8) | (qr > 1e-8)).any(axis=1)).mean())
-    # The cost of a step depends on the model state through the microphysics (the ideal case rains out): outside the timed region,
-    # the same K steps once more after 100 further steps, as a second window next to the headline one (informational).
-    later = None
-    if args.steps > 0 and not args.no_later_window and not args.no_cpu_baseline:      # (the full line only, like the traffic probe)
-        run_steps(d, opt, 100)
-        barrier()
-        t1 = time.perf_counter()
-        run_steps(d, opt, args.steps)
-        barrier()
-        later_ms = (time.perf_counter() - t1) / args.steps * 1e3
-        if world > 1:
-            t = torch.tensor([later_ms], dtype=torch.float64, device=red_device)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            later_ms = float(t.item())
-        if rank == 0:
-            qc = d.get("cloud_water_mass"); qr = d.get("rain_mass")
-            later = {"after_steps": args.warmup + args.steps + diag_steps + 100, "steps": args.steps, "ms_per_step": later_ms,
-                     "mp_active_column_fraction": float((((qc > 1e-8) | (qr > 1e-8)).any(axis=1)).mean())}
     if rank == 0:
         out = {
             "metric": "grid-cell updates/sec (advection+microphysics)",
@@ -465,45 +583,14 @@ def main():
                        # MPDATA either the fused kernel (every cell within 1e-5 of the local field scale per step, measured <= 8.1e-7: profiles/r06_parity.json) or,
                        # with --mpdata-exact, the reference's operation order (bit-identical; tests/test_gpu_trajectory.py)
                        "mpdata_arithmetic": ("reference operation order (bit-identical)" if args.mpdata_exact else "fused kernel (<= 1e-5 of the local scale per step)") if args.adv == "mpdata" else "n/a",
-                       "dt_s": dt, "mp_active_column_fraction": active},
-            "later_window": later,
-            "roofline": {"bound": "hbm", "kernel": "advect (k_upwind_pass + k_mpx_velocities + k_mpx_limit_donor: icar_hip_mpdata_exact)" if (args.mpdata_exact and args.adv == "mpdata")
-                                                   else f"advect ({ADVECT_KERNELS[args.adv]})",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_source, "algorithmic_bytes": alg_bytes, "avg_ms": adv_ms,
-                         # mp_ms_per_step / setup_ms_per_step: over the `timer_window_steps` steps that FOLLOW the timed region (see above)
-                         "mp_ms_per_step": mp_ms_step, "timer_window_steps": diag_steps,
-                         # the once-per-step setup of the advection (Courant winds + the scalar-independent MPDATA coefficients),
-                         # issued beside the interior microphysics; not part of avg_ms
-                         "setup_ms_per_step": winds_ms,
-                         # the advection GROUP of a step = advect() + its setup kernels, whatever they run beside: same algorithmic
-                         # bytes (the setup reads nothing the 8N+16 model does not already count) over the sum of the two timers
-                         "group_ms": adv_ms + winds_ms,
-                         "frac_group": (alg_bytes / ((adv_ms + winds_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS) if adv_ms + winds_ms > 0 else None,
-                         # informational: scalar-cell updates/s of the advection alone, and the measured
-                         # streaming-copy bandwidth of this box beside the spec peak that `frac` uses
-                         "advect_scalar_cell_updates_per_s": (mem_cells * nscal / (adv_ms * 1e-3)) if adv_ms > 0 else None,
-                         "measured_copy_GBps": stream_gbs,
-                         "frac_of_measured_copy": (achieved / stream_gbs) if stream_gbs else None},
-            # informational: the microphysics is VALU-bound, its share of the step and its algorithmic traffic
-            "microphysics": {"kernel": {"thompson": "k_thompson_pack", "simple": "k_mp_simple_pack", "wsm3": "k_wsm3", "wsm6": "k_w6"}.get(args.mp, "none"), "bound": "valu",
-                             "ms_per_step": mp_ms_step,
-                             "algorithmic_GBps": (mem_cells * (84 if args.mp == "thompson" else 56) / (mp_ms_step * 1e-3) / 1e9) if mp_ms_step > 0 else 0.0},
+                       "dt_s": dt},
         }
-        if world == 1 and not args.no_traffic_probe and not args.no_cpu_baseline and not args.mpdata_exact:        # (the full line only: profiling scripts pass --no-cpu-baseline)
-            # roofline.traffic measured NOW on this box (counters cannot be read inside this process: two child runs under rocprofv3)
-            t = probe_traffic(args)
-            if t is not None:
-                out["roofline"].update({"traffic": t[0], "traffic_read_bytes": t[1], "traffic_write_bytes": t[2],
-                                        "traffic_setup_bytes": t[3], "traffic_group": t[0] + t[3],
-                                        "traffic_group_over_algorithmic": (t[0] + t[3]) / alg_bytes,
-                                        "traffic_source": "live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, FETCH_SIZE x 2 for gfx950) over "
-                                                          "3-step child runs of this configuration, mean per dispatch of " + ADVECT_KERNELS[args.adv]})
-        if not args.no_cpu_baseline and world == 1:          # the CPU legs are timed at N=1 only (the other ranks would idle at the barrier)
-            out["cpu_baseline"] = cpu_baseline(args, nscal)
-            r = cpu_reference(args, nscal)
-            if r is not None:
-                out["cpu_reference"] = r
+    if args.full:
+        extra = full_figures(args, d, lib, world, rank, device, red_device, nscal, barrier, stepper)
+        if rank == 0:
+            out["config"]["mp_active_column_fraction"] = extra.pop("mp_active_column_fraction")
+            out.update(extra)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     d.close()
     if in_group:

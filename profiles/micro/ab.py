@@ -1,7 +1,7 @@
 """Noise-aware A/B of builds of libicar_hip.so on ONE lease (>= 5 alternating runs per arm, median and
 spread, keep only if the medians differ by more than the spread):
     python profiles/micro/ab.py [-n 5] [--bench-args "..."] name=path/to/lib.so [name=path ...]
-Each round runs every arm once, in rotating order; every run is a fresh `python bench.py --no-cpu-baseline --no-traffic-probe
+Each round runs every arm once, in rotating order; every run is a fresh `python bench.py --full --no-cpu-baseline --no-traffic-probe
 --no-later-window` process with ICAR_HIP_LIB pointing at the arm.  Prints one line per arm: median [min .. max] of ms/step, the
 advection's and the microphysics' event-timer averages, and appends everything to gpurun_out/ab_<tag>.jsonl."""
 import json, os, statistics, subprocess, sys
@@ -19,7 +19,7 @@ for r in range(n):
     order = arms[r % len(arms):] + arms[:r % len(arms)]
     for k, lib in order:
         env = dict(os.environ, ICAR_HIP_LIB=lib)
-        cmd = [sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-traffic-probe", "--no-later-window", "--steps", "20", "--warmup", "5"] + bench_args.split()
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-traffic-probe", "--no-later-window", "--steps", "20", "--warmup", "5"] + bench_args.split()
         try:
             out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300).stdout.strip().splitlines()[-1]
             d = json.loads(out); rf = d["roofline"]

@@ -5,7 +5,7 @@ for rep in 1 2; do
 for so in icar_amd/lib/ab/lib_*.so; do
   n=$(basename $so .so)
   echo "$n $(ICAR_HIP_LIB=$R/$so timeout 120 python profiles/prof_thompson.py 2>&1 | tail -1)"
-  ICAR_HIP_LIB=$R/$so timeout 200 python bench.py --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 | python -c "
+  ICAR_HIP_LIB=$R/$so timeout 200 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('$n', 'ms/step %.3f' % d['ms_per_step'], 'advect %.4f' % (r.get('avg_ms') or 0), 'mp %.4f' % (r.get('mp_ms_per_step') or 0))"

@@ -47,6 +47,9 @@ CASES = {
     "thompson_warm_24x12x30": dict(kind="th", nx=24, ny=12, nz=30, hill=1000.0, moist=1.6, cool=1.0, dt=40.0, nsteps=12),
     "thompson_cold_20x10x40": dict(kind="th", nx=20, ny=10, nz=40, hill=1000.0, moist=2.0, cool=2.0, dt=60.0, nsteps=25),
     "thompson_longdt_16x8x40": dict(kind="th", nx=16, ny=8, nz=40, hill=1000.0, moist=2.5, cool=3.0, dt=130.0, nsteps=30),
+    # another seed and noise level than the cases above (tests/test_oracle_thompson.py::test_column_physics_vs_reference_fresh_seed)
+    "thompson_fresh_seed_18x9x35": dict(kind="th", nx=18, ny=9, nz=35, hill=700.0, moist=2.2, cool=1.7, dt=75.0, nsteps=15,
+                                        noise=0.03, seed=99),
     "thompson_tables": dict(kind="thtab"),
     # a second, non-default mp_options set (opt_types.f90:30-41 order; both efficiency-table flags on): its own table cache
     "thompson_alt_tables": dict(kind="thtab", mp=ALT_MP, flags=[1, 1], cache="/tmp/oracle/run_alt"),
@@ -120,7 +123,7 @@ def run_case(name):
     elif p["kind"] == "th":
         nx, ny, nz = p["nx"], p["ny"], p["nz"]
         _th_init(ref, p)
-        c = ideal.make_case(nx, ny, nz, hill_height=p["hill"], noise=0.01)
+        c = ideal.make_case(nx, ny, nz, hill_height=p["hill"], noise=p.get("noise", 0.01), seed=p.get("seed", 1234))
         s = {k: c[k].copy() for k in TH_KEYS + ["exner", "pressure", "dz_mass"]}
         s["water_vapor"] = (s["water_vapor"] * np.float32(p["moist"])).astype(np.float32)
         ins = {"in_" + k: s[k].copy() for k in s}
@@ -132,7 +135,7 @@ def run_case(name):
                          1, nx, 1, ny, 1, nz, 2, nx - 1, 2, ny - 1, 1, nz)
             s["potential_temperature"] -= np.float32(p["cool"])
         out = {k: s[k] for k in TH_KEYS}
-        out.update({k: acc[k] for k in ("rainnc", "snownc", "graupelnc")})
+        out.update({k: acc[k] for k in ("rainnc", "snownc", "graupelnc", "sr")})
         out.update(ins)
     else:
         nx, ny, nz = p["nx"], p["ny"], p["nz"]

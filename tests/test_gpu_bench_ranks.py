@@ -7,6 +7,7 @@ import json
 import os
 import subprocess
 import sys
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -124,3 +125,31 @@ def test_a_failed_rccl_init_is_an_error_unless_the_host_transport_is_asked_for()
     assert r.returncode != 0
     assert "ICAR_ALLOW_HOST_STAGED=1" in r.stderr and "RCCL communicator is not available on every image" in r.stderr
     assert '"value"' not in r.stdout
+
+
+def test_bench_plain_line_carries_the_headline_and_full_the_rest():
+    """A plain run does only what the headline needs; --full adds the figures that take runs of their own."""
+    plain = _line(_run(["--gpus", "1"] + SMALL, {}))
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(plain) and plain["steps"] == 2
+    assert not {"roofline", "microphysics", "later_window", "cpu_baseline"} & set(plain)
+    full = _line(_run(["--gpus", "1", "--full"] + SMALL, {}))
+    assert full["roofline"]["avg_ms"] > 0 and full["microphysics"]["ms_per_step"] > 0 and full["steps"] == 2
+    assert 0.0 < full["config"]["mp_active_column_fraction"] <= 1.0
+
+
+def test_bench_dump_outputs_repeat_bit_for_bit(tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same arrays, float32 / float64, a sample of the larger fields"""
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--nx", "96", "--ny", "96", "--nz", "40"]
+    for run in ("a", "b"):
+        r = _run(args + ["--dump-outputs", str(tmp_path / run)], {})
+        assert r.returncode == 0, r.stderr[-3000:]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "water_vapor.npy" in names and "dt.npy" in names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape, n
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f"{n}: the two runs differ"
+        total += a.nbytes
+    assert np.load(tmp_path / "a" / "water_vapor.npy").size == 1 << 18       # 96 x 40 x 96 cells: the fixed sample
+    assert total <= 64 << 20
