@@ -43,9 +43,14 @@ struct IcarStepState {
     bool winds_first = true;                 // wind.f90:297 `.not. allocated(domain%sintheta)`: update_winds has not run yet
 };
 
-// the arrays of icar_hip_ctx::mpc, each of the tile's shape (k_mpdata_coef in mpdata.hip says what they hold): the first nine are the
-// antidiffusive coefficients of the x / y / z faces, the last two the denominators jaco rho and dz jaco rho of the donor-cell passes
+// component indices of the per-cell coefficients in icar_hip_ctx::mpc (k_mpdata_coef in mpdata.hip says what they hold): the first
+// nine are the antidiffusive coefficients of the x / y / z faces, the last two the denominators jaco rho and dz jaco rho of the
+// donor-cell passes.  They are stored as tuples, not as arrays: floats [3 n3 f, 3 n3 (f+1)) hold face f's (x, y, z) tuple
+// {MPC_A?, MPC_C??, MPC_C??} of every cell (12 B stride), so the first MPC_GH n3 floats are exactly the nine antidiffusive
+// coefficients; behind them, from mpc_cell_bytes(n3) on, one 16-B tuple {GH, GV, U_m, W_m} per cell (copies of icar_hip_ctx::U, W).
 enum { MPC_AU = 0, MPC_CUV, MPC_CUW, MPC_AV, MPC_CVU, MPC_CVW, MPC_AW, MPC_CWU, MPC_CWV, MPC_GH, MPC_GV, MPC_N };
+__host__ __device__ inline size_t mpc_cell_bytes(size_t n3) { return (MPC_GH * n3 * sizeof(float) + 255) & ~(size_t)255; }
+__host__ __device__ inline size_t mpc_bytes(size_t n3) { return mpc_cell_bytes(n3) + 4 * n3 * sizeof(float); }
 
 struct icar_hip_ctx {
     int device = 0;
@@ -62,7 +67,7 @@ struct icar_hip_ctx {
     float *dqdt[ICAR_N_FIELDS] = {nullptr};    // variable_t%dqdt_3d mirrors (apply_forcing)
     // advection scratch (A1-A5)
     float *U = nullptr, *V = nullptr, *W = nullptr, *Wdz = nullptr;
-    float *mpc = nullptr;                // MPDATA: the MPC_N scalar-independent coefficient arrays of this step's winds (mpdata.hip)
+    float *mpc = nullptr;                // MPDATA: the scalar-independent coefficients of this step's winds, mpc_bytes(n3) (MPC_* above)
     int mpc_dens = -1;
     float *alt[ICAR_N_ADVECTABLE] = {nullptr};   // ping-pong partner of each advected scalar
     float *mpx_buf = nullptr;            // mpdata_exact.hip: q2 (x2), u2, v2, w2 of mpx_nv scalars and the limited velocities of one

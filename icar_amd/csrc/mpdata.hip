@@ -32,15 +32,19 @@
 // Everything that does not depend on the scalar is computed ONCE per step by k_mpdata_coef (icar_hip_setup_winds) and loaded:
 // per face the antidiffusive coefficient |U|(1-|U|/Gbar)/2 and the two cross-term factors U Ubar_perp / (8 Gbar) (the six 4-point
 // transverse Courant averages, the 1/(G_i + G_i-1), the ground / top / x-ring zeros folded in, the z faces already times dz), and
-// per cell the two denominators jaco rho, dz jaco rho of the donor-cell passes -- eleven arrays (round 2 recomputed all of it for each
-// of the 9 scalars: ~50 of 252 VALU instructions per scalar-cell).  They and U_m, V_m, W_m are re-read per scalar from L2 (60 B per
-// cell against the 8 B of the scalar itself), which is why blocks of the same (tile, chunk) and different scalars are scheduled
-// onto the same XCD.
+// per cell the two denominators jaco rho, dz jaco rho of the donor-cell passes (round 2 recomputed all of it for each of the 9 scalars:
+// ~50 of 252 VALU instructions per scalar-cell).  They and U_m, V_m, W_m are re-read per scalar from L2 (60 B per cell against the
+// 8 B of the scalar itself), which is why blocks of the same (tile, chunk) and different scalars are scheduled onto the same XCD.
 //
 // Round 6: what the kernel is bound by is its LOADS IN FLIGHT, not its arithmetic (at two waves per SIMD ~1 % of its time per load of
 // a step's ~80; eight more VALU instructions per cell measured as nothing, profiles/r06_steps.md).  Hence: the donor-cell pass divides
 // exactly (bit-identical q2, see exact_quot) with computed reciprocals, and the plane's final update one step later takes those
 // reciprocals from it (registers / thread-private LDS) instead of loading them -- 81 loads per step where round 5 had 91.
+//
+// Round 7: the coefficients are stored as TUPLES and loaded wide (ctx.h): per face {A, C, C} in 12 B (buffer_load_dwordx3), per cell
+// {GH, GV, U_m, W_m} in 16 B (buffer_load_dwordx4; U_m and W_m are copies of c->U and c->W made by k_mpdata_coef, so the donor-cell
+// pass's U and W come with the denominators).  The same values, loaded by 34 instructions per step instead of 81: 16 face
+// tuples, 5 cell tuples, W of the slot below the wave, V of the next plane's north face and the 7 slots of the scalar.
 #include "ctx.h"
 #include <algorithm>
 #include <cmath>
@@ -90,25 +94,31 @@ __device__ __forceinline__ float min3f(float a, float b, float c) { return fminf
 // column) + scalar byte offset (plane and level, wave-uniform).  With flat addressing every one of the ~80 loads of a step
 // paid a 64-bit VALU add for its address (v_lshl_add_u64).
 using rsrc_t = __amdgpu_buffer_rsrc_t;
+typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ rsrc_t mkrsrc(const float *p) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, -1, 0x00020000); }
 __device__ __forceinline__ float ldb(rsrc_t r, int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0)); }
+__device__ __forceinline__ u32x3 ldb3(rsrc_t r, int voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b96(r, voff, soff, 0); }     // buffer_load_dwordx3
+__device__ __forceinline__ u32x4 ldb4(rsrc_t r, int voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0); }    // buffer_load_dwordx4
+__device__ __forceinline__ float fu(unsigned x) { return __uint_as_float(x); }
 __device__ __forceinline__ void stb(rsrc_t r, int voff, int soff, float v) { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, voff, soff, 0); }
 // ------------------------------------------------------------------------------------------------
-// scalar-independent coefficients of the corrective iteration (mpdata_fluxes, adv_mpdata.f90:107-255), once per step
-// eleven arrays of the tile's shape in one buffer (MPC_* = index of the array):
-//   x face (i-1/2) of cell (i,k,j):        au, cuv, cuw
-//   y face between j-1 and j:              av, cvu, cvw
-//   z face above level k:                  (aw, cwu, cwv) * dz(k) ; zero for the top level (w2(kme) = 0, :214)
-//   cell:                                  Gh = jaco rho, Gv = (dz jaco) rho -- the denominators of the donor-cell passes in the
-//                                          reference's association (adv_mpdata.f90:86-99): exact_quot() in k_mpdata_fused
+// scalar-independent coefficients of the corrective iteration (mpdata_fluxes, adv_mpdata.f90:107-255), once per step, as tuples of
+// the tile's cells in one buffer (ctx.h: MPC_* = component, mpc_bytes(n3) bytes):
+//   floats [0, 3 n3):       x face (i-1/2) of cell (i,k,j):   {au, cuv, cuw}
+//   floats [3 n3, 6 n3):    y face between j-1 and j:         {av, cvu, cvw}
+//   floats [6 n3, 9 n3):    z face above level k:             {aw, cwu, cwv} * dz(k) ; zero for the top level (w2(kme) = 0, :214)
+//   from byte mpc_cell_bytes(n3) (256-B aligned), 16 B per cell: {Gh, Gv, U_m, W_m} -- Gh = jaco rho, Gv = (dz jaco) rho, the
+//                           denominators of the donor-cell passes in the reference's association (adv_mpdata.f90:86-99: exact_quot()
+//                           in k_mpdata_fused), and copies of the Courant winds U and W (not W / dz) that the donor-cell pass reads
 // a? = |C| (1 - 2 |C| / (G + G')) / 2 ;  c?? = C (sum of the 4 transverse Courant numbers around the face) / (16 (G + G'))
 // with G = jaco [rho]; cross terms through the ground / column top (k-1, k+1 missing) and in the x ring are zero.
 // ------------------------------------------------------------------------------------------------
 // (enum MPC_*: ctx.h)
 template <bool RHO>
 __global__ void __launch_bounds__(256)
-k_mpdata_coef(Dims d, const float *__restrict__ U, const float *__restrict__ V, const float *__restrict__ Wz, const float *__restrict__ rho,
-              const float *__restrict__ jaco, const float *__restrict__ dz, float *__restrict__ C)
+k_mpdata_coef(Dims d, const float *__restrict__ U, const float *__restrict__ V, const float *__restrict__ Wz, const float *__restrict__ W,
+              const float *__restrict__ rho, const float *__restrict__ jaco, const float *__restrict__ dz, float *__restrict__ C)
 {
     const size_t n3 = (size_t)d.nx * d.nz * d.ny;
     const int i = blockIdx.x * 64 + threadIdx.x, k = blockIdx.y * 4 + threadIdx.y, j = blockIdx.z;
@@ -120,13 +130,14 @@ k_mpdata_coef(Dims d, const float *__restrict__ U, const float *__restrict__ V, 
     const int c = at(i, k, j);
     const bool xin = (i > 0) && (i < nx - 1), kin = (k > 0) && (k < nz - 1);
     const float g = G(i, k, j), dzc = dz[c];
+    float *const Cx = C + 3 * (size_t)c, *const Cy = Cx + 3 * n3, *const Cz = Cx + 6 * n3;     // the cell's face tuples
     // x face (i-1/2)
     {
         const float rG = frcp(g + G(iL, k, j));
         const float evv = (V[c] + V[at(i, k, jN)]) + (V[at(iL, k, j)] + V[at(iL, k, jN)]);
         const float evw = (Wz[c] + Wz[at(i, kB, j)]) + (Wz[at(iL, k, j)] + Wz[at(iL, kB, j)]);
         const float Uc = U[c], aU = fabsf(Uc), c0 = 0.0625f * Uc * rG;
-        C[MPC_AU * n3 + c] = 0.5f * aU * (1.0f - 2.0f * aU * rG); C[MPC_CUV * n3 + c] = c0 * evv; C[MPC_CUW * n3 + c] = kin ? c0 * evw : 0.0f;
+        Cx[0] = 0.5f * aU * (1.0f - 2.0f * aU * rG); Cx[1] = c0 * evv; Cx[2] = kin ? c0 * evw : 0.0f;
     }
     // y face between j-1 and j
     {
@@ -134,7 +145,7 @@ k_mpdata_coef(Dims d, const float *__restrict__ U, const float *__restrict__ V, 
         const float evu = (U[at(i, k, jP)] + U[c]) + (U[at(iR, k, jP)] + U[at(iR, k, j)]);
         const float evw = (Wz[at(i, k, jP)] + Wz[at(i, kB, jP)]) + (Wz[c] + Wz[at(i, kB, j)]);
         const float Vc = V[c], aV = fabsf(Vc), c0 = 0.0625f * Vc * rG;
-        C[MPC_AV * n3 + c] = 0.5f * aV * (1.0f - 2.0f * aV * rG); C[MPC_CVU * n3 + c] = xin ? c0 * evu : 0.0f; C[MPC_CVW * n3 + c] = kin ? c0 * evw : 0.0f;
+        Cy[0] = 0.5f * aV * (1.0f - 2.0f * aV * rG); Cy[1] = xin ? c0 * evu : 0.0f; Cy[2] = kin ? c0 * evw : 0.0f;
     }
     // z face above level k
     if (k < nz - 1) {
@@ -142,11 +153,11 @@ k_mpdata_coef(Dims d, const float *__restrict__ U, const float *__restrict__ V, 
         const float evu = (U[c] + U[at(i, kT, j)]) + (U[at(iR, k, j)] + U[at(iR, kT, j)]);
         const float evv = (V[c] + V[at(i, k, jN)]) + (V[at(i, kT, j)] + V[at(i, kT, jN)]);
         const float Wc = Wz[c], aW = fabsf(Wc), c0 = 0.0625f * Wc * rG;
-        C[MPC_AW * n3 + c] = 0.5f * aW * (1.0f - 2.0f * aW * rG) * dzc; C[MPC_CWU * n3 + c] = xin ? c0 * evu * dzc : 0.0f; C[MPC_CWV * n3 + c] = c0 * evv * dzc;
-    } else { C[MPC_AW * n3 + c] = 0.f; C[MPC_CWU * n3 + c] = 0.f; C[MPC_CWV * n3 + c] = 0.f; }
+        Cz[0] = 0.5f * aW * (1.0f - 2.0f * aW * rG) * dzc; Cz[1] = xin ? c0 * evu * dzc : 0.0f; Cz[2] = c0 * evv * dzc;
+    } else { Cz[0] = 0.f; Cz[1] = 0.f; Cz[2] = 0.f; }
     // (ring cells keep their value, adv_mpdata.f90:63-65: k_mpdata_fused multiplies their flux differences by zero)
     const float gh = g, gv = RHO ? (dzc * jaco[c]) * rho[c] : dzc * jaco[c];        // (dz * jaco * rho is evaluated left to right)
-    C[MPC_GH * n3 + c] = gh; C[MPC_GV * n3 + c] = gv;
+    ((float4 *)((char *)C + mpc_cell_bytes(n3)))[c] = make_float4(gh, gv, U[c], W[c]);
 }
 
 // mode of one step of the march: generic (any plane, rolls by copying) or one half of a steady pair (its exchange-buffer parity)
@@ -180,8 +191,8 @@ template <int KB, bool FCT, bool PASS1, bool EXACT>
 // the allocator takes if allowed) they wait for the launch to end -- the advection alone is then 5 % faster, the step 2 % slower.
 __global__ void __launch_bounds__(64 * MP_NW) __attribute__((amdgpu_num_vgpr(124)))
 k_mpdata_fused(Dims d, CVarPtrs qin, VarPtrs qout,
-               const float *__restrict__ Ug, const float *__restrict__ Vg, const float *__restrict__ Wg,
-               const float *__restrict__ Cg, unsigned asz, int clen, int ntile, int nchunk, int nscal, int nkr, int kstore)
+               const float *__restrict__ Vg, const float *__restrict__ Wg,   // (U comes with the cell tuples of Cg)
+               const float *__restrict__ Cg, unsigned fsz, unsigned cbase, int clen, int ntile, int nchunk, int nscal, int nkr, int kstore)
 {
     constexpr int H = KB + 2;                       // own levels + one halo level below and above
     // exchange slots, double-buffered by step parity (a step without plane-P work has only the first exchange)
@@ -236,8 +247,8 @@ k_mpdata_fused(Dims d, CVarPtrs qin, VarPtrs qout,
     float *__restrict__ outp = qout.p[0];
 #pragma unroll
     for (int mm = 1; mm < ICAR_MAX_ADV; ++mm) if (mm == m) { qp = qin.p[mm]; outp = qout.p[mm]; }   // (a dynamic index would put the tables in scratch)
-    const rsrc_t q = mkrsrc(qp), out = mkrsrc(outp), Ur = mkrsrc(Ug), Vr = mkrsrc(Vg), Wr = mkrsrc(Wg),
-                 cr = mkrsrc(Cg);                           // the eleven coefficient arrays, asz bytes each
+    const rsrc_t q = mkrsrc(qp), out = mkrsrc(outp), Vr = mkrsrc(Vg), Wr = mkrsrc(Wg),
+                 cr = mkrsrc(Cg);                           // the coefficient tuples: x / y / z faces (fsz bytes each), then the cells from cbase
 
     const int i = 1 - MP_HL + tile * MP_XOUT + lane;
     const int ic = min(max(i, 0), nx - 1);                  // lanes outside the domain are copies of the ring column
@@ -291,7 +302,13 @@ k_mpdata_fused(Dims d, CVarPtrs qin, VarPtrs qout,
     }
 
 #define LDQ(h, po) ldb(q, vk[h], (po))
-#define LDC(a, h, po) ldb(cr, vk[h], (int)((unsigned)(a) * asz + (unsigned)(po)))   /* coefficient array a (MPC_*); unsigned: the eleven arrays may span up to 4 GiB */
+// Coefficient tuples (ctx.h): 12 B per cell and face, 16 B per cell, so the byte offset of slot h is 3 vk[h] / 4 vk[h] and the
+// plane's 3 po / 4 po.  vk[h] is passed through an empty asm first: the compiler would otherwise hoist the 14 products out of
+// the march and keep them in VGPRs (one VALU per tuple load instead).  unsigned: the tuples may span up to 4 GiB.
+#define VK3(h) ([&] { int t_ = vk[h]; asm volatile("" : "+v"(t_)); return 3 * t_; }())
+#define VK4(h) ([&] { int t_ = vk[h]; asm volatile("" : "+v"(t_)); return 4 * t_; }())
+#define LDF(f, v3, po) ldb3(cr, (v3), (int)((unsigned)(f) * fsz + 3u * (unsigned)(po)))   /* face f (0 x, 1 y, 2 z): {A, C, C} */
+#define LDG(v4, po) ldb4(cr, (v4), (int)(cbase + 4u * (unsigned)(po)))                    /* cell: {GH, GV, U_m, W_m} */
 #define CLAMPJ(p) min(max((p), 0), ny - 1)
 
     // ---- rolling state (planes relative to the step's in-plane index P; N = P+1, M = P-1) ----
@@ -322,9 +339,12 @@ k_mpdata_fused(Dims d, CVarPtrs qin, VarPtrs qout,
 // group A: what the donor-cell pass of step PP reads (plane PP+1; the north face's V on plane PP+2)
 #define ISSUE_LOADS_A(oN_, oNN_)                                                                                         \
     {                                                                                                                    \
-        _Pragma("unroll") for (int h = 0; h <= KB; ++h) WN[h] = ldb(Wr, vk[h], (oN_));                                   \
-        _Pragma("unroll") for (int kk = 0; kk < KB; ++kk) { UN[kk] = ldb(Ur, vk[kk + 1], (oN_)); VNN[kk] = ldb(Vr, vk[kk + 1], (oNN_)); } \
-        _Pragma("unroll") for (int kk = 0; kk < KB; ++kk) { ghN[kk] = LDC(MPC_GH, kk + 1, (oN_)); gvN[kk] = LDC(MPC_GV, kk + 1, (oN_)); } \
+        WN[0] = ldb(Wr, vk[0], (oN_));                                                                                   \
+        _Pragma("unroll") for (int kk = 0; kk < KB; ++kk) {                                                              \
+            const u32x4 g_ = LDG(VK4(kk + 1), (oN_));                                                                    \
+            ghN[kk] = fu(g_.x); gvN[kk] = fu(g_.y); UN[kk] = fu(g_.z); WN[kk + 1] = fu(g_.w);                             \
+        }                                                                                                                \
+        _Pragma("unroll") for (int kk = 0; kk < KB; ++kk) VNN[kk] = ldb(Vr, vk[kk + 1], (oNN_));                         \
     }
     {
         const int o0 = CLAMPJ(P0) * sj4, o1 = CLAMPJ(P0 + 1) * sj4, o2 = CLAMPJ(P0 + 2) * sj4;
@@ -357,9 +377,11 @@ k_mpdata_fused(Dims d, CVarPtrs qin, VarPtrs qout,
         // face coefficients -- is issued here; each group back to back: loads placed next to their use were waited for one by one.
         float avN[KB], cvuN[KB], cvwN[KB], auP[KB], cuvP[KB], cuwP[KB];
 #pragma unroll
-        for (int kk = 0; kk < KB; ++kk) { avN[kk] = LDC(MPC_AV, kk + 1, oN); cvuN[kk] = LDC(MPC_CVU, kk + 1, oN); cvwN[kk] = LDC(MPC_CVW, kk + 1, oN); }
-#pragma unroll
-        for (int kk = 0; kk < KB; ++kk) { auP[kk] = LDC(MPC_AU, kk + 1, oP); cuvP[kk] = LDC(MPC_CUV, kk + 1, oP); cuwP[kk] = LDC(MPC_CUW, kk + 1, oP); }
+        for (int kk = 0; kk < KB; ++kk) {
+            const int v3 = VK3(kk + 1);
+            const u32x3 a = LDF(1, v3, oN), b = LDF(0, v3, oP);
+            avN[kk] = fu(a.x); cvuN[kk] = fu(a.y); cvwN[kk] = fu(a.z); auP[kk] = fu(b.x); cuvP[kk] = fu(b.y); cuwP[kk] = fu(b.z);
+        }
         __builtin_amdgcn_sched_barrier(0);
 
         // ================= S1: donor-cell pass on plane N, its extrema and x/z differences =================
@@ -454,7 +476,7 @@ k_mpdata_fused(Dims d, CVarPtrs qin, VarPtrs qout,
         // vmcnt counts in order, so cache-resident loads issued behind an HBM load are waited for as long as that one
         float awP[KB + 1], cwuP[KB + 1], cwvP[KB + 1];
 #pragma unroll
-        for (int h = 0; h <= KB; ++h) { awP[h] = LDC(MPC_AW, h, oP); cwuP[h] = LDC(MPC_CWU, h, oP); cwvP[h] = LDC(MPC_CWV, h, oP); }
+        for (int h = 0; h <= KB; ++h) { const u32x3 z = LDF(2, VK3(h), oP); awP[h] = fu(z.x); cwuP[h] = fu(z.y); cwvP[h] = fu(z.z); }
         {
             const int o3 = (STEADY ? P + 3 : CLAMPJ(P + 3)) * sj4;
             if (STEADY) {
@@ -677,7 +699,10 @@ k_mpdata_fused(Dims d, CVarPtrs qin, VarPtrs qout,
     }
 #undef ISSUE_LOADS_A
 #undef LDQ
-#undef LDC
+#undef LDF
+#undef LDG
+#undef VK3
+#undef VK4
 #undef MP_POST
 #undef MP_WAIT
 #undef CLAMPJ
@@ -692,7 +717,7 @@ static void launch_fused(icar_hip_ctx *c, bool fct, bool pass1, bool exact, cons
 {
     const unsigned nitem = (unsigned)(ntile * nchunk * nkr * nv), cap = (nitem + 7u) / 8u;
     const dim3 g(8u * cap), b(64, nw);                      // block id = xcd + 8 * slot, slot < cap
-#define GO(F, P1, E) hipLaunchKernelGGL((k_mpdata_fused<KB, F, P1, E>), g, b, 0, c->stream, c->d, in, out, c->U, c->V, c->W, c->mpc, (unsigned)(c->n3 * sizeof(float)), clen, ntile, nchunk, nv, nkr, kstore)
+#define GO(F, P1, E) hipLaunchKernelGGL((k_mpdata_fused<KB, F, P1, E>), g, b, 0, c->stream, c->d, in, out, c->V, c->W, c->mpc, (unsigned)(3 * c->n3 * sizeof(float)), (unsigned)mpc_cell_bytes(c->n3), clen, ntile, nchunk, nv, nkr, kstore)
 #define GO2(F, P1) { if (exact) GO(F, P1, true); else GO(F, P1, false); }
     if (fct) { if (pass1) GO2(true, true) else GO2(true, false) } else { if (pass1) GO2(false, true) else GO2(false, false) }
 #undef GO2
@@ -705,11 +730,11 @@ int icar_mpdata_coef_run(icar_hip_ctx *c, bool rho_on)
     const float *jaco = icar_field_f(c, ICAR_F_JACOBIAN), *dz = icar_field_f(c, ICAR_F_ADVECTION_DZ);
     const float *rho = rho_on ? icar_field_f(c, ICAR_F_DENSITY) : nullptr;
     if (!jaco || !dz || (rho_on && !rho)) return 1;
-    if (c->n3 * sizeof(float) * MPC_N >= ((size_t)1 << 32)) { icar_set_error("mpdata: a tile of more than 97 M cells is not supported (32-bit buffer offsets into the coefficient arrays)"); return 1; }
-    if (!c->mpc) HIPCHK(hipMalloc(&c->mpc, c->n3 * sizeof(float) * MPC_N));
+    if (mpc_bytes(c->n3) >= ((size_t)1 << 32)) { icar_set_error("mpdata: a tile of more than 82 M cells is not supported (32-bit buffer offsets into the coefficient tuples)"); return 1; }
+    if (!c->mpc) HIPCHK(hipMalloc(&c->mpc, mpc_bytes(c->n3)));
     const dim3 g((c->d.nx + 63) / 64, (c->d.nz + 3) / 4, c->d.ny), b(64, 4);
-    if (rho_on) hipLaunchKernelGGL(k_mpdata_coef<true>, g, b, 0, c->stream, c->d, c->U, c->V, c->Wdz, rho, jaco, dz, c->mpc);
-    else        hipLaunchKernelGGL(k_mpdata_coef<false>, g, b, 0, c->stream, c->d, c->U, c->V, c->Wdz, rho, jaco, dz, c->mpc);
+    if (rho_on) hipLaunchKernelGGL(k_mpdata_coef<true>, g, b, 0, c->stream, c->d, c->U, c->V, c->Wdz, c->W, rho, jaco, dz, c->mpc);
+    else        hipLaunchKernelGGL(k_mpdata_coef<false>, g, b, 0, c->stream, c->d, c->U, c->V, c->Wdz, c->W, rho, jaco, dz, c->mpc);
     HIPCHK(hipGetLastError());
     c->mpc_dens = rho_on ? 1 : 0;
     return 0;
