@@ -9,12 +9,18 @@
 //                  context's second stream (time_step.f90:512-526).
 //   halo_retrieve  unpack kernel (all directions, one launch, the reference's N, S, E, W precedence at the corners);
 //                  stream order IS the `sync images`.
+//   exchange_uv    the staggered u / v boxes of iterative_winds (exchange_u / exchange_v), one message per neighbour.
 //   co_min         ncclAllReduce of one value on the device.
 //
 // Edges that wrap around to the tile itself (a periodic single image, what src/tests/test_mpdata.f90 does by hand) use the
 // same pack / unpack kernels and no transport.  A second transport, host-staged through POSIX shared memory, exists for boxes
 // with fewer GPUs than images (RCCL refuses two ranks on one device): the same entry points, the same kernels, the
 // messages PUT into the neighbour's inbox by the CPU.  It is a functional path (tests, 1-GPU boxes), never a benchmark.
+//
+// Halos and u / v boxes keep their buffers in one MsgSet each and move through the same two functions, post (every peer's
+// send) and complete (every peer's receive), so each transport's point-to-point code exists once.  The one-rank self-rings
+// of tests/test_gpu_comm.py (the image is its own neighbour, over RCCL and over the host-staged transport) run all of it for
+// both kinds of message; an N-rank run differs in the peer rank only.
 //
 // librccl.so.1 is opened on the first icar_hip_comm_init with more than a local topology (573 MB; single-image users of
 // the library never load it).
@@ -103,13 +109,19 @@ __global__ void k_stamp_check(Dims d, const float *__restrict__ f, int h, float 
 
 }  // namespace
 
+// One kind of message (the halos, or the u / v boxes of exchange_uv), per direction N, S, E, W.
+struct MsgSet {
+    float *send[4] = {}, *recv[4] = {};                      // device
+    float *hsend[4] = {}, *hrecv[4] = {};                    // pinned staging, host-staged transport only
+    size_t cap_send[4] = {}, cap_recv[4] = {};               // elements allocated
+    size_t n_send[4] = {}, n_recv[4] = {};                   // elements of the message in flight
+};
+
 struct IcarComm {
     int kind = ICAR_COMM_LOCAL;
     int nranks = 1, rank = 0;
     int nb[4] = {ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_NONE};
-    float *sbuf[4] = {nullptr, nullptr, nullptr, nullptr}, *rbuf[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t cap[4] = {0, 0, 0, 0};                            // elements allocated per direction
-    size_t cnt[4] = {0, 0, 0, 0};                            // elements of the message in flight per direction
+    MsgSet halo, uv;
     bool in_flight = false;
     // RCCL
     ncclComm_t nccl = nullptr;
@@ -117,12 +129,7 @@ struct IcarComm {
     double *h_red = nullptr;                                 // pinned
     // host-staged
     std::string shm_name; void *shm = nullptr; size_t shm_bytes = 0, slot_bytes = 0;
-    float *hs[4] = {nullptr, nullptr, nullptr, nullptr}, *hr[4] = {nullptr, nullptr, nullptr, nullptr};   // pinned staging
-    uint64_t msg_no = 0, red_no = 0;
-    // exchange_u / exchange_v messages (one per neighbour, both fields): device send / receive buffers, pinned staging
-    float *uvs[4] = {nullptr, nullptr, nullptr, nullptr}, *uvr[4] = {nullptr, nullptr, nullptr, nullptr};
-    float *uvhs[4] = {nullptr, nullptr, nullptr, nullptr}, *uvhr[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t uvcap_s[4] = {0, 0, 0, 0}, uvcap_r[4] = {0, 0, 0, 0};
+    uint64_t msg_no = 0, red_no = 0;                         // msg_no numbers halo and u / v messages alike
 
     ShmBox *box(int r, int d) const { return (ShmBox *)((char *)shm + 64 + ((size_t)r * 5 + d) * 64); }
     ShmRed *red(int r) const { return (ShmRed *)((char *)shm + 64 + ((size_t)r * 5 + 4) * 64); }
@@ -132,27 +139,42 @@ struct IcarComm {
 static bool has_peer(const IcarComm *m, int d) { return m->nb[d] >= 0; }
 static bool wraps(const IcarComm *m, int d) { return m->nb[d] == ICAR_NEIGHBOR_SELF; }
 
-static int ensure_buffers(icar_hip_ctx *c, IcarComm *m, int h, int nf)
+bool icar_comm_has_peers(icar_hip_ctx *c)
+{
+    if (!c->comm) return false;
+    for (int d = 0; d < 4; ++d) if (has_peer(c->comm, d)) return true;
+    return false;
+}
+
+// the next message of set s: ns[d] elements out and nr[d] in towards d (0 = nothing to allocate); pinned staging for the peers
+// of a host-staged communicator only
+static int reserve(IcarComm *m, MsgSet &s, const size_t ns[4], const size_t nr[4])
 {
     for (int d = 0; d < 4; ++d) {
-        if (m->nb[d] == ICAR_NEIGHBOR_NONE) { m->cnt[d] = 0; continue; }
-        const size_t n = icar_hip_halo_count(c, d, h) * (size_t)nf;
-        m->cnt[d] = n;
-        if (n <= m->cap[d]) continue;
-        if (m->sbuf[d]) { hipFree(m->sbuf[d]); m->sbuf[d] = nullptr; }
-        if (m->rbuf[d]) { hipFree(m->rbuf[d]); m->rbuf[d] = nullptr; }
-        m->cap[d] = 0;                                       // nothing usable until every allocation below has succeeded
-        HIPCHK(hipMalloc(&m->sbuf[d], n * sizeof(float)));
-        if (has_peer(m, d)) HIPCHK(hipMalloc(&m->rbuf[d], n * sizeof(float)));
-        if (m->kind == ICAR_COMM_HOST && has_peer(m, d)) {
-            if (m->hs[d]) hipHostFree(m->hs[d]);
-            if (m->hr[d]) hipHostFree(m->hr[d]);
-            HIPCHK(hipHostMalloc((void **)&m->hs[d], n * sizeof(float), hipHostMallocDefault));
-            HIPCHK(hipHostMalloc((void **)&m->hr[d], n * sizeof(float), hipHostMallocDefault));
-        }
-        m->cap[d] = n;
+        auto grow = [&](size_t n, float *&dev, float *&pinned, size_t &cap) {
+            if (n <= cap) return 0;
+            if (dev) { (void)hipFree(dev); dev = nullptr; }
+            if (pinned) { (void)hipHostFree(pinned); pinned = nullptr; }
+            cap = 0;                                         // nothing usable until every allocation below has succeeded
+            HIPCHK(hipMalloc(&dev, n * sizeof(float)));
+            if (m->kind == ICAR_COMM_HOST && has_peer(m, d)) HIPCHK(hipHostMalloc((void **)&pinned, n * sizeof(float), hipHostMallocDefault));
+            cap = n;
+            return 0;
+        };
+        s.n_send[d] = ns[d]; s.n_recv[d] = nr[d];
+        if (grow(ns[d], s.send[d], s.hsend[d], s.cap_send[d]) || grow(nr[d], s.recv[d], s.hrecv[d], s.cap_recv[d])) return 1;
     }
     return 0;
+}
+
+static void release(MsgSet &s)
+{
+    for (int d = 0; d < 4; ++d) {
+        if (s.send[d]) hipFree(s.send[d]);
+        if (s.recv[d]) hipFree(s.recv[d]);
+        if (s.hsend[d]) hipHostFree(s.hsend[d]);
+        if (s.hrecv[d]) hipHostFree(s.hrecv[d]);
+    }
 }
 
 template <class Pred>
@@ -170,44 +192,80 @@ static int spin_until(Pred p, const char *what)
     return 0;
 }
 
+// ---- the transport: post sends every peer's message, complete receives every peer's message -------------------------
+// Peers need RCCL or the host-staged transport.  Both callers check before they pack; icar_hip_comm_init refuses peers
+// without a unique id, so no communicator fails this today.
+static int check_transport(icar_hip_ctx *c, const char *who)
+{
+    const int k = c->comm->kind;
+    if (k == ICAR_COMM_RCCL || k == ICAR_COMM_HOST || !icar_comm_has_peers(c)) return 0;
+    icar_set_error(std::string(who) + ": neighbours given but no transport (icar_hip_comm_init with a unique id, or _init_host)");
+    return 1;
+}
+
+static int post(icar_hip_ctx *c, IcarComm *m, MsgSet &s, const char *who)
+{
+    if (m->kind == ICAR_COMM_RCCL) {
+        // what I send towards d arrives at the peer as coming from opposite(d).  Sends are posted N, S, E, W and receives in the
+        // order of the matching sends of the peer (from S, N, W, E), so two images that are each other's neighbour in both
+        // directions of an axis (a periodic pair) pair their messages correctly: RCCL matches per peer in posting order.
+        ScopedTimer t(c, "halo_transport");
+        NCHK(g_rccl.GroupStart());
+        for (int d = 0; d < 4; ++d) if (has_peer(m, d)) NCHK(g_rccl.Send(s.send[d], s.n_send[d], ncclFloat, m->nb[d], m->nccl, c->stream));
+        for (int d = 0; d < 4; ++d) { const int o = opposite(d); if (has_peer(m, o)) NCHK(g_rccl.Recv(s.recv[o], s.n_recv[o], ncclFloat, m->nb[o], m->nccl, c->stream)); }
+        NCHK(g_rccl.GroupEnd());
+        return 0;
+    }
+    for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {
+        if (s.n_send[d] * sizeof(float) > m->slot_bytes) { icar_set_error(std::string(who) + ": message larger than the slot_bytes given to icar_hip_comm_init_host"); return 1; }
+        HIPCHK(hipMemcpyAsync(s.hsend[d], s.send[d], s.n_send[d] * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));                 // the packs (and a sub-step's strips); the interior launch on the second stream keeps running
+    ++m->msg_no;
+    for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {
+        const int p = m->nb[d], o = opposite(d);
+        ShmBox *b = m->box(p, o);
+        const uint64_t want = m->msg_no - 1;
+        if (spin_until([&] { return b->ack.load(std::memory_order_acquire) >= want; }, who)) return 1;
+        memcpy(m->slot(p, o), s.hsend[d], s.n_send[d] * sizeof(float));       // the PUT
+        b->seq.store(m->msg_no, std::memory_order_release);
+    }
+    return 0;
+}
+
+static int complete(icar_hip_ctx *c, IcarComm *m, MsgSet &s, const char *who)
+{
+    if (m->kind != ICAR_COMM_HOST) return 0;                 // RCCL: stream order is the `sync images`
+    for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {
+        ShmBox *b = m->box(m->rank, d);
+        if (spin_until([&] { return b->seq.load(std::memory_order_acquire) >= m->msg_no; }, who)) return 1;   // sync images
+        memcpy(s.hrecv[d], m->slot(m->rank, d), s.n_recv[d] * sizeof(float));
+        b->ack.store(m->msg_no, std::memory_order_release);
+        HIPCHK(hipMemcpyAsync(s.recv[d], s.hrecv[d], s.n_recv[d] * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    return 0;
+}
+
 // ---- halo_send / halo_retrieve (domain_obj.f90:109-143) --------------------------------------------------------------
 int icar_comm_halo_send(icar_hip_ctx *c, int h, const int *fields, int nf)
 {
     IcarComm *m = c->comm;
     if (!m || nf <= 0) return 0;
     if (m->in_flight) { icar_set_error("halo_send: the previous halo_send has not been retrieved"); return 1; }
-    if (ensure_buffers(c, m, h, nf)) return 1;
+    if (check_transport(c, "halo_send")) return 1;
+    // a send buffer on every edge that is not a domain boundary (retrieve unpacks a wrapping edge from the opposite edge's
+    // send buffer), a receive buffer where there is a peer
+    size_t ns[4], nr[4];
     int dirs[4], nd = 0; void *bufs[4];
-    for (int d = 0; d < 4; ++d) if (m->nb[d] != ICAR_NEIGHBOR_NONE) { dirs[nd] = d; bufs[nd] = m->sbuf[d]; ++nd; }
+    for (int d = 0; d < 4; ++d) {
+        ns[d] = m->nb[d] == ICAR_NEIGHBOR_NONE ? 0 : icar_hip_halo_count(c, d, h) * (size_t)nf;
+        nr[d] = has_peer(m, d) ? ns[d] : 0;
+    }
+    if (reserve(m, m->halo, ns, nr)) return 1;
+    for (int d = 0; d < 4; ++d) if (m->nb[d] != ICAR_NEIGHBOR_NONE) { dirs[nd] = d; bufs[nd] = m->halo.send[d]; ++nd; }
     if (!nd) return 0;
     if (icar_halo_pack_dirs(c, nd, dirs, h, fields, nf, bufs, false)) return 1;      // put_<dir> of every variable, one launch
-    bool peers = false;
-    for (int d = 0; d < 4; ++d) peers = peers || has_peer(m, d);
-    if (peers && m->kind == ICAR_COMM_RCCL) {
-        // what I send towards d arrives at the peer as coming from opposite(d).  Sends are posted N, S, E, W and receives in the
-        // order of the matching sends of the peer (from S, N, W, E), so two images that are each other's neighbour in both
-        // directions of an axis (a periodic pair) pair their messages correctly: RCCL matches per peer in posting order.
-        ScopedTimer t(c, "halo_transport");
-        NCHK(g_rccl.GroupStart());
-        for (int d = 0; d < 4; ++d) if (has_peer(m, d)) NCHK(g_rccl.Send(m->sbuf[d], m->cnt[d], ncclFloat, m->nb[d], m->nccl, c->stream));
-        for (int d = 0; d < 4; ++d) { const int o = opposite(d); if (has_peer(m, o)) NCHK(g_rccl.Recv(m->rbuf[o], m->cnt[o], ncclFloat, m->nb[o], m->nccl, c->stream)); }
-        NCHK(g_rccl.GroupEnd());
-    } else if (peers && m->kind == ICAR_COMM_HOST) {
-        for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {
-            if (m->cnt[d] * sizeof(float) > m->slot_bytes) { icar_set_error("halo_send: message larger than the slot_bytes given to icar_hip_comm_init_host"); return 1; }
-            HIPCHK(hipMemcpyAsync(m->hs[d], m->sbuf[d], m->cnt[d] * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));                 // the strips + pack; the interior launch on the second stream keeps running
-        ++m->msg_no;
-        for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {
-            const int p = m->nb[d], o = opposite(d);
-            ShmBox *b = m->box(p, o);
-            const uint64_t want = m->msg_no - 1;
-            if (spin_until([&] { return b->ack.load(std::memory_order_acquire) >= want; }, "halo_send")) return 1;
-            memcpy(m->slot(p, o), m->hs[d], m->cnt[d] * sizeof(float));             // the PUT
-            b->seq.store(m->msg_no, std::memory_order_release);
-        }
-    } else if (peers) { icar_set_error("halo_send: neighbours given but no transport (icar_hip_comm_init with a unique id, or _init_host)"); return 1; }
+    if (icar_comm_has_peers(c) && post(c, m, m->halo, "halo_send")) return 1;
     m->in_flight = true;
     return 0;
 }
@@ -218,22 +276,14 @@ int icar_comm_halo_retrieve(icar_hip_ctx *c, int h, const int *fields, int nf)
     if (!m || nf <= 0) return 0;
     if (!m->in_flight) { icar_set_error("halo_retrieve without a halo_send"); return 1; }
     m->in_flight = false;
-    if (m->kind == ICAR_COMM_HOST) {
-        for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {
-            ShmBox *b = m->box(m->rank, d);
-            if (spin_until([&] { return b->seq.load(std::memory_order_acquire) >= m->msg_no; }, "halo_retrieve")) return 1;   // sync images
-            memcpy(m->hr[d], m->slot(m->rank, d), m->cnt[d] * sizeof(float));
-            b->ack.store(m->msg_no, std::memory_order_release);
-            HIPCHK(hipMemcpyAsync(m->rbuf[d], m->hr[d], m->cnt[d] * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        }
-    }
-    // one unpack launch for everything that arrived: from a peer at d its message (rbuf[d]); at a wrapping edge d what my own
-    // opposite edge packed (sbuf[opposite(d)]).  N/S rows leave the corner cells to an E/W message of the same call (the
+    if (complete(c, m, m->halo, "halo_retrieve")) return 1;
+    // one unpack launch for everything that arrived: from a peer at d its message (recv[d]); at a wrapping edge d what my own
+    // opposite edge packed (send[opposite(d)]).  N/S rows leave the corner cells to an E/W message of the same call (the
     // reference retrieves N, S, E, W in that order, exchangeable_obj.f90:138-151).
     int dirs[4], nd = 0; void *bufs[4];
     for (int d = 0; d < 4; ++d) {
-        if (has_peer(m, d)) { dirs[nd] = d; bufs[nd] = m->rbuf[d]; ++nd; }
-        else if (wraps(m, d) && wraps(m, opposite(d))) { dirs[nd] = d; bufs[nd] = m->sbuf[opposite(d)]; ++nd; }
+        if (has_peer(m, d)) { dirs[nd] = d; bufs[nd] = m->halo.recv[d]; ++nd; }
+        else if (wraps(m, d) && wraps(m, opposite(d))) { dirs[nd] = d; bufs[nd] = m->halo.send[opposite(d)]; ++nd; }
     }
     if (!nd) return 0;
     return icar_halo_pack_dirs(c, nd, dirs, h, fields, nf, bufs, true);
@@ -264,90 +314,34 @@ void uv_plan(int nx, int ny, int h, int dir, UvBox send[2], UvBox recv[2])
     }
 }
 size_t uv_count(const UvBox b[2], int nz) { return ((size_t)b[0].ni * b[0].nj + (size_t)b[1].ni * b[1].nj) * nz; }
-}  // namespace
-
-bool icar_comm_has_peers(icar_hip_ctx *c)
+// the two boxes of one message, back to back in buf
+int uv_copy(icar_hip_ctx *c, const UvBox b[2], int which, float *buf, bool unpack)
 {
-    if (!c->comm) return false;
-    for (int d = 0; d < 4; ++d) if (has_peer(c->comm, d)) return true;
-    return false;
+    for (int k = 0; k < 2; ++k) {
+        if (icar_box_copy(c, b[k].f, which, b[k].i0, b[k].ni, b[k].j0, b[k].nj, buf, unpack)) return 1;
+        buf += (size_t)b[k].ni * b[k].nj * c->d.nz;
+    }
+    return 0;
 }
+}  // namespace
 
 int icar_comm_exchange_uv(icar_hip_ctx *c, int h, int which)
 {
     IcarComm *m = c->comm;
-    if (!m) return 0;
-    bool peers = false;
-    for (int d = 0; d < 4; ++d) peers = peers || has_peer(m, d);
-    if (!peers) return 0;                                   // (edges that wrap to the tile itself are not exchanged: the reference has none)
+    if (!icar_comm_has_peers(c)) return 0;                  // (edges that wrap to the tile itself are not exchanged: the reference has none)
     if (m->in_flight) { icar_set_error("exchange_uv between a halo_send and its halo_retrieve"); return 1; }
-    if (m->kind != ICAR_COMM_RCCL && m->kind != ICAR_COMM_HOST) { icar_set_error("exchange_uv: neighbours given but no transport"); return 1; }
+    if (check_transport(c, "exchange_uv")) return 1;
     const Dims &dd = c->d;
     if (h < 1 || 2 * h + 1 > dd.nx || 2 * h + 1 > dd.ny) { icar_set_error("exchange_uv: bad halo width"); return 1; }
     UvBox sb[4][2], rb[4][2]; size_t ns[4] = {0, 0, 0, 0}, nr[4] = {0, 0, 0, 0};
     for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {
         uv_plan(dd.nx, dd.ny, h, d, sb[d], rb[d]);
         ns[d] = uv_count(sb[d], dd.nz); nr[d] = uv_count(rb[d], dd.nz);
-        if (ns[d] > m->uvcap_s[d]) {
-            if (m->uvs[d]) { (void)hipFree(m->uvs[d]); m->uvs[d] = nullptr; }
-            if (m->uvhs[d]) { (void)hipHostFree(m->uvhs[d]); m->uvhs[d] = nullptr; }
-            m->uvcap_s[d] = 0;
-            HIPCHK(hipMalloc(&m->uvs[d], ns[d] * sizeof(float)));
-            if (m->kind == ICAR_COMM_HOST) HIPCHK(hipHostMalloc((void **)&m->uvhs[d], ns[d] * sizeof(float), hipHostMallocDefault));
-            m->uvcap_s[d] = ns[d];
-        }
-        if (nr[d] > m->uvcap_r[d]) {
-            if (m->uvr[d]) { (void)hipFree(m->uvr[d]); m->uvr[d] = nullptr; }
-            if (m->uvhr[d]) { (void)hipHostFree(m->uvhr[d]); m->uvhr[d] = nullptr; }
-            m->uvcap_r[d] = 0;
-            HIPCHK(hipMalloc(&m->uvr[d], nr[d] * sizeof(float)));
-            if (m->kind == ICAR_COMM_HOST) HIPCHK(hipHostMalloc((void **)&m->uvhr[d], nr[d] * sizeof(float), hipHostMallocDefault));
-            m->uvcap_r[d] = nr[d];
-        }
-        size_t off = 0;
-        for (int b = 0; b < 2; ++b) {
-            const UvBox &x = sb[d][b];
-            if (icar_box_copy(c, x.f, which, x.i0, x.ni, x.j0, x.nj, m->uvs[d] + off, false)) return 1;
-            off += (size_t)x.ni * x.nj * dd.nz;
-        }
     }
-    if (m->kind == ICAR_COMM_RCCL) {
-        ScopedTimer t(c, "halo_transport");
-        NCHK(g_rccl.GroupStart());
-        for (int d = 0; d < 4; ++d) if (has_peer(m, d)) NCHK(g_rccl.Send(m->uvs[d], ns[d], ncclFloat, m->nb[d], m->nccl, c->stream));
-        for (int d = 0; d < 4; ++d) { const int o = opposite(d); if (has_peer(m, o)) NCHK(g_rccl.Recv(m->uvr[o], nr[o], ncclFloat, m->nb[o], m->nccl, c->stream)); }
-        NCHK(g_rccl.GroupEnd());
-    } else {
-        for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {
-            if (ns[d] * sizeof(float) > m->slot_bytes) { icar_set_error("exchange_uv: message larger than the slot_bytes given to icar_hip_comm_init_host"); return 1; }
-            HIPCHK(hipMemcpyAsync(m->uvhs[d], m->uvs[d], ns[d] * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        ++m->msg_no;
-        for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {
-            const int p = m->nb[d], o = opposite(d);
-            ShmBox *b = m->box(p, o);
-            const uint64_t want = m->msg_no - 1;
-            if (spin_until([&] { return b->ack.load(std::memory_order_acquire) >= want; }, "exchange_uv")) return 1;
-            memcpy(m->slot(p, o), m->uvhs[d], ns[d] * sizeof(float));
-            b->seq.store(m->msg_no, std::memory_order_release);
-        }
-        for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {
-            ShmBox *b = m->box(m->rank, d);
-            if (spin_until([&] { return b->seq.load(std::memory_order_acquire) >= m->msg_no; }, "exchange_uv")) return 1;
-            memcpy(m->uvhr[d], m->slot(m->rank, d), nr[d] * sizeof(float));
-            b->ack.store(m->msg_no, std::memory_order_release);
-            HIPCHK(hipMemcpyAsync(m->uvr[d], m->uvhr[d], nr[d] * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        }
-    }
-    for (int d = 0; d < 4; ++d) if (has_peer(m, d)) {       // north, south, then east, west
-        size_t off = 0;
-        for (int b = 0; b < 2; ++b) {
-            const UvBox &x = rb[d][b];
-            if (icar_box_copy(c, x.f, which, x.i0, x.ni, x.j0, x.nj, m->uvr[d] + off, true)) return 1;
-            off += (size_t)x.ni * x.nj * dd.nz;
-        }
-    }
+    if (reserve(m, m->uv, ns, nr)) return 1;
+    for (int d = 0; d < 4; ++d) if (has_peer(m, d) && uv_copy(c, sb[d], which, m->uv.send[d], false)) return 1;
+    if (post(c, m, m->uv, "exchange_uv") || complete(c, m, m->uv, "exchange_uv")) return 1;
+    for (int d = 0; d < 4; ++d) if (has_peer(m, d) && uv_copy(c, rb[d], which, m->uv.recv[d], true)) return 1;   // north, south, then east, west
     return 0;
 }
 
@@ -399,16 +393,8 @@ void icar_comm_free(icar_hip_ctx *c)
 {
     IcarComm *m = c->comm;
     if (!m) return;
-    for (int d = 0; d < 4; ++d) {
-        if (m->sbuf[d]) hipFree(m->sbuf[d]);
-        if (m->rbuf[d]) hipFree(m->rbuf[d]);
-        if (m->hs[d]) hipHostFree(m->hs[d]);
-        if (m->hr[d]) hipHostFree(m->hr[d]);
-        if (m->uvs[d]) hipFree(m->uvs[d]);
-        if (m->uvr[d]) hipFree(m->uvr[d]);
-        if (m->uvhs[d]) hipHostFree(m->uvhs[d]);
-        if (m->uvhr[d]) hipHostFree(m->uvhr[d]);
-    }
+    release(m->halo);
+    release(m->uv);
     if (m->d_red) hipFree(m->d_red);
     if (m->h_red) hipHostFree(m->h_red);
     if (m->nccl) g_rccl.CommDestroy(m->nccl);
@@ -420,10 +406,19 @@ void icar_comm_free(icar_hip_ctx *c)
     c->comm = nullptr;
 }
 
-static int check_neighbors(int nranks, const int nb[4])
+// the prologue of both initialisers: the argument checks, then a new communicator with these neighbours replaces the old one
+static int comm_open(icar_hip_ctx *c, int nranks, int rank, const int nb[4], bool null_arg, const char *who)
 {
+    if (null_arg) { icar_set_error(std::string(who) + ": null argument"); return 1; }
+    if (nranks < 1 || rank < 0 || rank >= nranks) { icar_set_error(std::string(who) + ": bad rank"); return 1; }
     for (int d = 0; d < 4; ++d)
         if (nb[d] >= nranks || nb[d] < ICAR_NEIGHBOR_SELF) { icar_set_error("comm_init: neighbors[] holds a rank of the communicator, ICAR_NEIGHBOR_NONE or ICAR_NEIGHBOR_SELF"); return 1; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    icar_comm_free(c);
+    c->comm = new IcarComm();
+    c->comm->nranks = nranks; c->comm->rank = rank;
+    memcpy(c->comm->nb, nb, sizeof c->comm->nb);
     return 0;
 }
 
@@ -442,20 +437,10 @@ int icar_hip_comm_unique_id(char uid[128])
 
 int icar_hip_comm_init(icar_hip_ctx *c, int nranks, int rank, const char uid[128], const int neighbors[4])
 {
-    if (!c || !neighbors) { icar_set_error("comm_init: null argument"); return 1; }
-    if (nranks < 1 || rank < 0 || rank >= nranks) { icar_set_error("comm_init: bad rank"); return 1; }
-    if (check_neighbors(nranks, neighbors)) return 1;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    icar_comm_free(c);
-    IcarComm *m = new IcarComm();
-    m->nranks = nranks; m->rank = rank;
-    memcpy(m->nb, neighbors, sizeof m->nb);
-    c->comm = m;
+    if (comm_open(c, nranks, rank, neighbors, !c || !neighbors, "comm_init")) return 1;
+    IcarComm *m = c->comm;
     if (!uid) {
-        bool peers = false;
-        for (int d = 0; d < 4; ++d) peers = peers || neighbors[d] >= 0;
-        if (nranks != 1 || peers) { icar_comm_free(c); icar_set_error("comm_init: several images need the unique id of icar_hip_comm_unique_id (broadcast from image 1)"); return 1; }
+        if (nranks != 1 || icar_comm_has_peers(c)) { icar_comm_free(c); icar_set_error("comm_init: several images need the unique id of icar_hip_comm_unique_id (broadcast from image 1)"); return 1; }
         m->kind = ICAR_COMM_LOCAL;
         return 0;
     }
@@ -469,19 +454,12 @@ int icar_hip_comm_init(icar_hip_ctx *c, int nranks, int rank, const char uid[128
 
 int icar_hip_comm_init_host(icar_hip_ctx *c, int nranks, int rank, const char *shm_name, size_t slot_bytes, const int neighbors[4])
 {
-    if (!c || !neighbors || !shm_name) { icar_set_error("comm_init_host: null argument"); return 1; }
-    if (nranks < 1 || rank < 0 || rank >= nranks) { icar_set_error("comm_init_host: bad rank"); return 1; }
-    if (check_neighbors(nranks, neighbors)) return 1;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    icar_comm_free(c);
-    IcarComm *m = new IcarComm();
-    m->kind = ICAR_COMM_HOST; m->nranks = nranks; m->rank = rank;
-    memcpy(m->nb, neighbors, sizeof m->nb);
+    if (comm_open(c, nranks, rank, neighbors, !c || !neighbors || !shm_name, "comm_init_host")) return 1;
+    IcarComm *m = c->comm;
+    m->kind = ICAR_COMM_HOST;
     m->shm_name = shm_name[0] == '/' ? shm_name : std::string("/") + shm_name;
     m->slot_bytes = (slot_bytes + 63) & ~(size_t)63;
     m->shm_bytes = 64 + (size_t)nranks * 5 * 64 + (size_t)nranks * 4 * m->slot_bytes;
-    c->comm = m;
     // every image opens (creating if need be) and sizes the same object; ftruncate to an equal size is idempotent and a new
     // object reads as zeros, so there is no creation order to respect.  The caller picks a name that is unique to the run.
     const int fd = shm_open(m->shm_name.c_str(), O_CREAT | O_RDWR, 0600);
