@@ -25,7 +25,8 @@
 //     limited flux of a face is min(1, beta, beta) times its unlimited flux (flux1 is linear in the velocity).
 //   * quotients are n * v_rcp_f32(d) (1 ulp): the scheme's 22 divisions per scalar-cell cost 11 instead of 50 cycles
 //     per wave each (profiles/micro/valubench.hip).  flux1(l, r, U) = ((U+|U|) l + (U-|U|) r)/2 is evaluated as
-//     U * (U > 0 ? l : r), which is the same number.  Results agree with the CPU reference to <= 8.1e-7 of the local field
+//     U * (U > 0 ? l : r), which is the same number while the product is a normal float (below FLT_MIN the reference rounds
+//     2 U l and then its half: up to one subnormal step apart).  Results agree with the CPU reference to <= 8.1e-7 of the local field
 //     scale (profiles/r06_parity.json); tests assert 1e-5 on every cell (north-star tolerance) and fail above 0.3 of it -- the donor-cell kernel of the upwind scheme
 //     (advect.hip) stays bit-exact.
 //
@@ -412,7 +413,8 @@ k_mpdata_fused(Dims d, CVarPtrs qin, VarPtrs qout,
                     // (qmax - q2) / 1e-15 clipped to 1 (adv_mpdata_FCT_core.f90:80-113 with fin = fout = 0 there) -- zero or one,
                     // decided by whether q2 of the ring's neighbour EQUALS an extremum: one ulp in q2 switches a whole antidiffusive
                     // flux on or off (round 5's contracted form: 9.2e-6 of theta at one cell of the config-3 tile).  Everything
-                    // downstream of q2 is continuous in its rounding errors.
+                    // downstream of q2 is continuous in its rounding errors.  (A flux below FLT_MIN is rounded once here, twice in the reference
+                    // (upw): q2 may then differ by a few subnormal steps, where (q2 - qmin) / 1e-15 is ~0 either way.)
                     const float FxL = opaque(upw(dpp_l(qN.v[h]), qN.v[h], UN[kk])), FxR = dpp_r(FxL);
                     const float Fn = opaque(upw(qN.v[h], qNN.v[h], VNN[kk]));
                     // ring cells keep their value (adv_mpdata.f90:63-65): the flux differences times 0 (rmN: the x ring's lanes, and
@@ -748,10 +750,12 @@ int icar_mpdata_fused_run(icar_hip_ctx *c, bool rho_on, bool fct, bool pass1, co
     if (nx < 3 || ny < 3) { icar_set_error("mpdata: tile must be at least 3 x 3 cells"); return 1; }
     if ((size_t)nx * nz * ny * sizeof(float) >= ((size_t)1 << 31)) { icar_set_error("mpdata: a field of 2 GiB or more is not supported (32-bit buffer offsets)"); return 1; }
     const int ntile = std::max(1, (nx - 2 + MP_XOUT - 1) / MP_XOUT);
-    // levels: one block holds at most MP_NW x MP_KB = 40; taller columns are cut into level ranges with MP_ZH halo levels
+    // levels: one block holds at most MP_NW x MP_KB = 40; taller columns are cut into level ranges with MP_ZH halo levels.  Every
+    // range's block computes its kstore levels and MP_ZH halo levels on either side, so it is those kstore + 2 MP_ZH that must fit
+    // (counting the halos once per cut let nz = 73..76, 109..112, ... through with 6 levels per thread: no such kernel)
     const int cap_lv = MP_NW * MP_KB;
     int nkr = 1;
-    while (nkr * cap_lv - 2 * MP_ZH * (nkr - 1) < nz) ++nkr;
+    while ((nz + nkr - 1) / nkr + (nkr > 1 ? 2 * MP_ZH : 0) > cap_lv) ++nkr;
     const int kstore = (nz + nkr - 1) / nkr;
     const int blk_lv = std::min(nz, kstore + (nkr > 1 ? 2 * MP_ZH : 0));       // levels a block computes
     const int kb = (blk_lv + MP_NW - 1) / MP_NW, nw = (blk_lv + kb - 1) / kb;
