@@ -1,5 +1,6 @@
 // icar_amd/csrc/column_comm.h -- how the levels of a column talk to each other when every thread owns ONE level.
-//   WaveComm  : one column per wave, level = lane; wave shuffles / ballot.  nz of 64 lanes are busy.
+//   WaveComm  : one column per wave, level = lane; wave shuffles / ballot.  nz of 64 lanes are busy.  Thompson takes it where
+//               the packing fills the lanes no better: 57 <= nz <= 64 (and nz = 1), thompson_launch_geometry() below.
 //   BlockComm : cpb whole columns per block, thread = level*cpb + column (column fastest: a wave spans few levels of
 //               neighbouring columns => coalesced rows and little divergence); the couplings go through LDS.
 // Used by the Thompson column (thompson_lane.inc) and by mp_simple (mp_simple.hip).
@@ -242,4 +243,23 @@ static inline float block_comm_geometry(int nz, int &nt, int &cpb)
         if (u > best + need) { best = u; nt = t; cpb = t / nz; }
     }
     return best;
+}
+
+// What Thompson launches for a column of nk levels (icar_thompson_run_tiles; tests/support/th_probe.hip reports it to the tests):
+// the packed layout unless one column per 64-lane wave fills the lanes as well (within 2 %) -- that is 57 <= nk <= 64; at
+// 52..56 levels nine columns in a 512-thread block are 98 % busy and stay packed -- and for the single level the packing has no
+// geometry for.  TH_LAUNCH_NONE: more levels than this build takes (nk > 1024).  Lane kernel: nt = 256 (four columns), cpb = 0.
+enum { TH_LAUNCH_NONE = 0, TH_LAUNCH_LANE = 1, TH_LAUNCH_PACK = 2 };
+static inline int thompson_launch_geometry(int nk, int &nt, int &cpb)
+{
+    nt = 0; cpb = 0;
+    if (nk < 1) return TH_LAUNCH_NONE;
+    if (nk >= 2) {
+        const float u = block_comm_geometry(nk, nt, cpb);
+        if (nk <= 64 && u <= nk / 64.0f + 0.02f) { cpb = 0; nt = 0; }
+    }
+    if (cpb) return TH_LAUNCH_PACK;
+    if (nk > 64) return TH_LAUNCH_NONE;
+    nt = 256;
+    return TH_LAUNCH_LANE;
 }

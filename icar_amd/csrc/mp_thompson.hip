@@ -254,13 +254,10 @@ int icar_thompson_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int (*t
     }
     if (nt_ == 0) return 0;
     ScopedTimer tm(c, "mp");
-    // Packed layout (column_comm.h) unless one column per 64-lane wave fills the lanes as well (52 <= nk <= 64).
+    // Packed layout unless one column per 64-lane wave fills the lanes as well (57 <= nk <= 64): column_comm.h
     int cpb = 0, nt = 0;
-    if (nk >= 2) {
-        const float u = block_comm_geometry(nk, nt, cpb);
-        if (nk <= 64 && u <= nk / 64.0f + 0.02f) { cpb = 0; nt = 0; }
-    }
-    if (cpb) {
+    const int kind = thompson_launch_geometry(nk, nt, cpb);
+    if (kind == TH_LAUNCH_PACK) {
         // all tiles in ONE launch: process_halo's four 1-cell strips are latency-bound when launched one after another
         ThTiles tl; tl.n = nt_; tl.off[0] = 0;
         tl.xcd_run = 64;                 // consecutive column groups (and a few rows of them) per XCD turn
@@ -280,7 +277,7 @@ int icar_thompson_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int (*t
         HIPCHK(hipGetLastError());
         return 0;
     }
-    if (nk > 64) { icar_set_error("thompson: this many levels are not supported by this build"); return 1; }
+    if (kind != TH_LAUNCH_LANE) { icar_set_error("thompson: this many levels are not supported by this build"); return 1; }
     for (int t = 0; t < nt_; ++t) {                      // one column per wave, level = lane
         const int its = T4[t][0], i_end = T4[t][1], jts = T4[t][2], j_end = T4[t][3];
         dim3 gl((i_end - its + 1 + 3) / 4, j_end - jts + 1), bl(256);

@@ -8,7 +8,7 @@
 //   * sedimentation fluxes from the level above, nstep sub-steps (:2660-2770)                -> neighbour read per sub-step
 // With thread = level, every per-level array of the reference is a register.  The couplings go through a communicator policy
 // (column_comm.h):
-//   WaveComm  : one column per wave, level = lane; wave shuffles / ballot.  nz of 64 lanes are busy (used for 52 <= nz <= 64).
+//   WaveComm  : one column per wave, level = lane; wave shuffles / ballot.  nz of 64 lanes are busy (used for 57 <= nz <= 64 and nz = 1: column_comm.h).
 //   BlockComm : cpb whole columns per block, thread = level*cpb + column (column fastest: a wave spans few levels of neighbouring
 //               columns => coalesced rows and little divergence); the couplings go through LDS.  240 of 256 threads busy at nz = 40.
 // Round 5: every coupling reads DOWNWARD and what it carries can be posted before a barrier, so the block form needs five block

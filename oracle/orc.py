@@ -120,6 +120,16 @@ def thompson(qv, qc, qr, qi, qs, qg, ni, nr, th, pii, p, dz, dt, rainnc, rainncv
                        *[_i(x) for x in (ids, ide, jds, jde, kds, kde, its, ite, jts, jte, kts, kte)])
 
 
+TH_DIAG_N = 8
+
+
+def thompson_diag(buf):
+    """buf = int32 (ny, nx, TH_DIAG_N), C order: every following thompson() records the sedimentation plan of each column it runs
+    there (oracle/thompson_column.c: orc_thompson_diag); None switches the record off.  The caller keeps buf alive."""
+    assert buf is None or (buf.dtype == np.int32 and buf.shape[-1] == TH_DIAG_N)
+    lib().orc_thompson_diag(_p(buf))
+
+
 def diagnostic_update(p, th, u, v, w, dzdx, dzdy, jaco):
     ny, nz, nx = p.shape
     out = {k: np.zeros((ny, nz, nx), np.float32) for k in ("exner", "pressure_interface", "temperature", "temperature_interface",

@@ -8,7 +8,29 @@
 #include <stdio.h>
 #include "thompson_oracle.h"
 
-#define KMAX 256
+#define KMAX 1024     /* the tallest column the device takes (icar_amd/csrc/column_comm.h) */
+
+/* Optional per-column record of the sedimentation plan (tests/mp_columns_case.py asserts on it that a case really exercises the
+ * exchanges it is meant for).  orc_thompson_diag(buf) with buf = int[ny * nx * TH_DIAG_N] switches it on, NULL off; of each column
+ * orc_thompson runs: [0..3] the sub-step counts of rain, cloud ice, snow, graupel; [4] the largest distance from a level that
+ * holds none of a species but falls with a speed copied from above (> 1e-3 m/s) to the level it copied from; [5] how many such
+ * copies over a distance >= 2 have their source at level index >= 64 and their own at <= 63; [6] the species (bits 0..3) with a
+ * copy over a distance >= 2.  A column that returns early (:1363) records zeros.  No effect on what the column computes. */
+#define TH_DIAG_N 8
+static int *g_th_diag = NULL;
+static __thread int th_diag_col[TH_DIAG_N];
+void orc_thompson_diag(int *buf) { g_th_diag = buf; }
+static void th_diag_species(int s, const int *has, const float *vt, int kts, int kte)
+{
+    int src = -1;                                   /* the nearest level above that holds the species */
+    for (int k = kte; k >= kts; --k) {
+        if (has[k]) { src = k; continue; }
+        if (src < 0 || !(vt[k] > 1.E-3f)) continue;
+        const int gap = src - k;
+        if (gap > th_diag_col[4]) th_diag_col[4] = gap;
+        if (gap >= 2) { th_diag_col[6] |= 1 << s; if (src >= 64 && k <= 63) ++th_diag_col[5]; }
+    }
+}
 
 /* Transcendental mode (see icar_oracle.c: orc_set_math_mode).  Mode 0 = libm float functions exactly as
  * the flang-compiled reference calls them (bit-identical to oracle/_ref).  Mode 1 = the same functions
@@ -610,6 +632,7 @@ void orc_thompson(int nx, int nz, int ny, float *qv, float *qc, float *qr, float
         for (int i = i_start; i <= i_end; ++i) {
             float qv1d[KMAX], qc1d[KMAX], qi1d[KMAX], qr1d[KMAX], qs1d[KMAX], qg1d[KMAX], ni1d[KMAX], nr1d[KMAX], t1d[KMAX], p1d[KMAX], dz1d[KMAX];
             float pptrain = 0.f, pptsnow = 0.f, pptgraul = 0.f, pptice = 0.f;
+            memset(th_diag_col, 0, sizeof th_diag_col);
             for (int k = kts; k <= kte; ++k) {
                 const size_t c = IDX3(i - 1, k - 1, j - 1);
                 const int kk = k - kts;
@@ -618,6 +641,7 @@ void orc_thompson(int nx, int nz, int ny, float *qv, float *qc, float *qr, float
             }
             th_column(qv1d, qc1d, qi1d, qr1d, qs1d, qg1d, ni1d, nr1d, t1d, p1d, dz1d, &pptrain, &pptsnow, &pptgraul, &pptice, nk, dt);
             const size_t c2 = (size_t)(i - 1) + (size_t)nx * (j - 1);
+            if (g_th_diag) memcpy(g_th_diag + TH_DIAG_N * c2, th_diag_col, sizeof th_diag_col);
             rainnc[c2] = rainnc[c2] + pptrain + pptsnow + pptgraul + pptice;
             if (snownc) snownc[c2] = snownc[c2] + pptsnow + pptice;
             if (graupelnc) graupelnc[c2] = graupelnc[c2] + pptgraul;

@@ -360,6 +360,13 @@
     }
     if (ksed1[3] == kte) ksed1[3] = kte - 1;
     if (nstep > 0) onstep[3] = 1.f / (float)nstep;
+    if (g_th_diag) {
+        int hr[KMAX], hi[KMAX], hs[KMAX], hg[KMAX];
+        for (k = kts; k <= kte; ++k) { hr[k] = rr[k] > R1; hi[k] = ri[k] > R1; hs[k] = rs[k] > R1; hg[k] = rg[k] > R1; }
+        for (n = 0; n < 4; ++n) th_diag_col[n] = (int)lroundf(1.f / onstep[n]);
+        th_diag_species(0, hr, vtrk, kts, kte); th_diag_species(1, hi, vtik, kts, kte);
+        th_diag_species(2, hs, vtsk, kts, kte); th_diag_species(3, hg, vtgk, kts, kte);
+    }
 
     /* ---- :2660-2770 sedimentation ---- */
     nstep = (int)lroundf(1.f / onstep[0]);

@@ -28,6 +28,7 @@ def lib():
     L.icar_probe_math.argtypes = [ci, ci, vp, vp, vp]
     L.icar_probe_dec_index.argtypes = [vp, vp, ci, ci, ci, vp]
     L.icar_probe_mpdata_zero_antidiffusion.argtypes = [vp]
+    L.icar_probe_launch_geometry.argtypes = [ci, vp, vp, vp, vp, vp]
     return L
 
 

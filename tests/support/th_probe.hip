@@ -4,6 +4,7 @@
 // tests/support/libicar_probe.so; libicar_hip.so exports no probe.
 #include <hip/hip_runtime.h>
 #include "thompson_math.h"
+#include "column_comm.h"
 
 namespace {
 __global__ void k_p10(float *p10) { for (int n = 0; n < TH_P10_N; ++n) p10[n] = powi10f(n - TH_P10_OFF); }     // as k_thompson_constants fills ThState::p10
@@ -56,6 +57,18 @@ int icar_probe_math(int op, int n, const double *x, const double *y, double *out
     CK(hipGetLastError()); CK(hipDeviceSynchronize());
     CK(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
     (void)hipFree(dx); (void)hipFree(dout); if (dy) (void)hipFree(dy);
+    return 0;
+}
+// what icar_thompson_run_tiles launches for a column of nk levels (column_comm.h: the function the dispatch itself calls; host
+// only, no device needed): *kind = 0 refused, 1 one column per wave (k_thompson_lane), 2 packed (k_thompson_pack); *nt = threads
+// per block, *cpb = columns per block (0 for the lane kernel); *mp_simple_nt / *mp_simple_cpb = what k_mp_simple_pack gets
+// (block_comm_geometry() as it comes; 0 / 0 = refused)
+int icar_probe_launch_geometry(int nk, int *kind, int *nt, int *cpb, int *mp_simple_nt, int *mp_simple_cpb)
+{
+    if (!kind || !nt || !cpb || !mp_simple_nt || !mp_simple_cpb) return 1;
+    *kind = thompson_launch_geometry(nk, *nt, *cpb);
+    *mp_simple_nt = *mp_simple_cpb = 0;
+    if (nk >= 1 && !(block_comm_geometry(nk, *mp_simple_nt, *mp_simple_cpb) > 0.0f)) *mp_simple_nt = *mp_simple_cpb = 0;
     return 0;
 }
 // exactly one of r4 / r8; n2 = the table's first decade

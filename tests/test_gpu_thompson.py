@@ -161,9 +161,11 @@ def test_thompson_excludes_last_global_row_and_column(th_oracle):
 
 @pytest.mark.parametrize("nz", [3, 12, 56, 100])
 def test_thompson_other_level_counts_vs_oracle(th_oracle, nz):
-    """nz=12: 21 columns per 256-thread block; nz=56: one column per wave; nz=100: 5 columns per 512-thread block (more levels than
-    a level mask holds: the exchanges scan flag words); nz=3: 85 columns per block, more than a wave has lanes (a wave then holds
-    one level of SOME columns: the per-wave minima of the others stay at the neutral element the kernel starts them with)."""
+    """nz=12: 21 columns per 256-thread block; nz=56: 9 columns per 512-thread block (98 % of the threads busy against 87.5 % of a
+    wave's lanes, so the dispatch keeps the packed kernel: the one-column-per-wave kernel runs at 57..64 levels and at 1,
+    tests/test_gpu_mp_columns.py); nz=100: 5 columns per 512-thread block (more levels than a level mask holds: the exchanges scan
+    flag words); nz=3: 85 columns per block, more than a wave has lanes (a wave then holds one level of SOME columns: the per-wave
+    minima of the others stay at the neutral element the kernel starts them with)."""
     out, ref = run_case(th_oracle, mode=0, nx=30 if nz > 3 else 200, ny=10, nz=nz, steps=8, cool=2.0, moist=2.0, dt=60.0,
                         uniform_dz=150.0 if nz == 100 else (2500.0 if nz == 3 else None))
     if nz > 3:

@@ -127,3 +127,51 @@ def field_stats(got, ref, rtol=1e-5):
     return {"bitdiff_frac": float((np.asarray(got) != np.asarray(ref).astype(np.asarray(got).dtype)).mean()),
             "beyond_rtol_frac": float(bad.mean()), "max_abs_over_max": float(np.abs(a - b).max() / scale),
             "max_pointwise_rel": pw, "cells": int(a.size)}
+
+
+# (species, bottom, top) in metres above the ground: separated layers with empty air between them.  The ideal case's 0 degC level lies
+# 2.7 .. 3.7 km above the ground before the cooling between calls lowers it: rain, graupel and snow below it, every species above it.
+HYDRO_LAYERS = [("rain", 300.0, 1500.0), ("graupel", 1900.0, 2500.0), ("snow", 2900.0, 3500.0), ("rain", 4200.0, 4600.0),
+                ("graupel", 5200.0, 5800.0), ("snow", 6400.0, 7200.0), ("cloud_ice", 7800.0, 8400.0), ("snow", 9000.0, 9500.0),
+                ("cloud_ice", 10000.0, 10800.0), ("graupel", 11300.0, 11800.0)]
+HYDRO_AMOUNT = {"rain": 2e-4, "graupel": 2e-4, "snow": 3e-4, "cloud_ice": 2e-5}
+HYDRO_NUMBER = {"rain": ("rain_number", 5e3), "cloud_ice": ("ice_number", 5e4)}
+
+
+def seed_layered_hydrometeors(c, species=("rain", "cloud_ice", "snow", "graupel")):
+    """Rain, cloud ice, snow and graupel of a case in separated layers (HYDRO_LAYERS; a level holds a layer if its centre lies in
+    it) with empty levels between them.  Columns differ: the layers are shifted by 0 .. 750 m and the amounts scaled by 1 .. 3 from
+    column to column, so that the nearest level above that holds a species, the fall speeds and with them the sedimentation
+    sub-step counts differ between neighbouring columns.  A species that no level of a column caught (levels thicker than the
+    layers) goes to one level of its own (rain lowest, ice highest).  With more than 66 levels each column also gets one species
+    (by turns) at level index 65 or 66 above empty levels 60 .. 64, so that a fall speed is carried down across level 63 / 64 --
+    the last lane of a wave, the last bit of a 64-bit level mask.  In place; returns c."""
+    f32 = np.float32
+    ny, nz, nx = c["dz_mass"].shape
+    dz = c["dz_mass"].astype(np.float64)
+    h = np.cumsum(dz, axis=1) - 0.5 * dz                                            # level centres above the ground
+    ii = np.arange(nx)[None, None, :]; jj = np.arange(ny)[:, None, None]
+    shift = 250.0 * ((3 * ii + 5 * jj) % 4)
+    amp = 1.0 + ((ii + 2 * jj) % 3)
+    q = {s: np.zeros((ny, nz, nx), np.float64) for s in species}
+    for s, lo, hi in HYDRO_LAYERS:
+        if s in q:
+            q[s] = np.where((h >= lo + shift) & (h < hi + shift), HYDRO_AMOUNT[s] * amp, q[s])
+    own = {"rain": min(1, nz - 1), "graupel": nz // 3, "snow": nz // 2, "cloud_ice": (3 * nz) // 4}
+    for s in q:
+        none = ~(q[s] > 0).any(axis=1)                                              # (ny, nx)
+        q[s][:, own[s], :] = np.where(none, HYDRO_AMOUNT[s] * amp[:, 0, :], q[s][:, own[s], :])
+    if nz > 66:
+        turn = ((ii + jj) % len(species))[:, 0, :]
+        hold = 65 + (np.arange(nx) % 2)[None, :]
+        for n, s in enumerate(species):
+            mine = (turn == n)[:, None, :] & np.ones((1, nz, 1), bool)
+            k = np.arange(nz)[None, :, None]
+            q[s] = np.where(mine & (k >= 60) & (k < hold[:, None, :]), 0.0, q[s])
+            q[s] = np.where(mine & (k == hold[:, None, :]), HYDRO_AMOUNT[s] * amp, q[s])
+    for s in q:
+        c[s] = q[s].astype(f32)
+        if s in HYDRO_NUMBER:
+            name, per_kg = HYDRO_NUMBER[s]
+            c[name] = np.where(q[s] > 0, per_kg, 0.0).astype(f32)     # (the same number for 1 .. 3 x the mass: sizes, hence speeds, differ)
+    return c
