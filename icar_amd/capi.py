@@ -30,6 +30,7 @@ SYMBOLS = [
     "icar_hip_linwinds_setup", "icar_hip_linwinds_terrain_frequency", "icar_hip_linear_perturbation",
     "icar_hip_linwinds_build_lut", "icar_hip_linwinds_build_lut_varying", "icar_hip_linwinds_lut_download", "icar_hip_linwinds_lut_upload", "icar_hip_linwinds_lut_entry",
     "icar_hip_linwinds_perturbation_download", "icar_hip_linwinds_perturbation_upload", "icar_hip_spatial_winds",
+    "icar_hip_pbl_simple", "icar_hip_pbl_configure", "icar_hip_pbl", "icar_hip_pbl_nsubsteps",
 ]
 
 
@@ -97,6 +98,10 @@ def lib():
         L.icar_hip_comm_unique_id.argtypes = [ctypes.c_char_p]
         L.icar_hip_halo_send.argtypes = [vp, ci, ctypes.POINTER(ci), ci]
         L.icar_hip_halo_retrieve.argtypes = [vp, ci, ctypes.POINTER(ci), ci]
+        L.icar_hip_pbl_simple.argtypes = [vp, ctypes.c_float, ci, ci, ci, ci, ci, ci]
+        L.icar_hip_pbl_configure.argtypes = [vp, ci]
+        L.icar_hip_pbl.argtypes = [vp, ctypes.c_float]
+        L.icar_hip_pbl_nsubsteps.argtypes = [vp, vp, ci]
         _lib = L
     return _lib
 

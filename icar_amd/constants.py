@@ -8,6 +8,11 @@ kMP_THOMPSON = 1
 kMP_SB04 = 2
 kMP_WSM6 = 4
 kMP_WSM3 = 6
+kPBL_BASIC = 1                  # icar_constants.f90:354-356
+kPBL_SIMPLE = 2
+kPBL_YSU = 3
+kLC_LAND = 1                    # land_mask values, icar_constants.f90
+kLC_WATER = 2
 kDEFAULT_HALO_SIZE = 1          # icar_constants.f90:320
 
 # advection dispatch order of mpdata()/upwind() (src/physics/adv_mpdata.f90:512-522);

@@ -26,7 +26,7 @@ size_t icar_field_count(const icar_hip_ctx *c, int f)
     const size_t nx = c->d.nx, nz = c->d.nz, ny = c->d.ny;
     if (f == ICAR_F_U || f == ICAR_F_JACOBIAN_U || f == ICAR_F_DZDX || f == ICAR_F_ZR_U) return (nx + 1) * nz * ny;
     if (f == ICAR_F_V || f == ICAR_F_JACOBIAN_V || f == ICAR_F_DZDY || f == ICAR_F_ZR_V) return nx * nz * (ny + 1);
-    if (field_is_2dd(f) || f == ICAR_F_SURFACE_PRESSURE || (f >= ICAR_F_IVT && f <= ICAR_F_IWI)) return nx * ny;
+    if (field_is_2dd(f) || f == ICAR_F_SURFACE_PRESSURE || (f >= ICAR_F_IVT && f <= ICAR_F_IWI) || f == ICAR_F_TERRAIN || f == ICAR_F_LAND_MASK) return nx * ny;
     return nx * nz * ny;
 }
 
@@ -456,6 +456,8 @@ int icar_hip_ctx_destroy(icar_hip_ctx *c)
     if (c->cfl_ev) hipEventDestroy(c->cfl_ev);
     if (c->iw_adj) hipFree(c->iw_adj);
     if (c->wgr_tmp) hipFree(c->wgr_tmp);
+    if (c->pbl_kq) hipFree(c->pbl_kq);
+    if (c->pbl_rowmax) hipFree(c->pbl_rowmax);
     icar_wsm3_free(c);
     icar_wsm6_free(c);
     icar_thompson_free(c);
@@ -521,6 +523,7 @@ int icar_hip_field_download(icar_hip_ctx *c, int f, void *host)
 
 __global__ void k_fill_f(float *p, size_t n, float v) { size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; if (t < n) p[t] = v; }
 __global__ void k_fill_d(double *p, size_t n, double v) { size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; if (t < n) p[t] = v; }
+__global__ void k_fill_i(int *p, size_t n, int v) { size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; if (t < n) p[t] = v; }
 
 int icar_hip_field_fill(icar_hip_ctx *c, int f, double value)
 {
@@ -530,6 +533,7 @@ int icar_hip_field_fill(icar_hip_ctx *c, int f, double value)
     if (!p) return 1;
     const size_t n = icar_field_count(c, f);
     if (field_is_2dd(f)) hipLaunchKernelGGL(k_fill_d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (double *)p, n, value);
+    else if (f == ICAR_F_LAND_MASK) hipLaunchKernelGGL(k_fill_i, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (int *)p, n, (int)value);
     else                 hipLaunchKernelGGL(k_fill_f, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, p, n, (float)value);
     HIPCHK(hipGetLastError());
     if (f == ICAR_F_U || f == ICAR_F_V || f == ICAR_F_W || (f >= ICAR_F_DENSITY && f <= ICAR_F_ADVECTION_DZ)) icar_winds_changed(c);
@@ -671,7 +675,7 @@ int icar_hip_dqdt_upload(icar_hip_ctx *c, int f, const void *host)
 {
     if (!c || !host) { icar_set_error("dqdt_upload: null argument"); return 1; }
     HIPCHK(hipSetDevice(c->device));
-    if (f < 0 || f >= ICAR_N_FIELDS || field_is_2dd(f)) { icar_set_error("dqdt_upload: bad field"); return 1; }
+    if (f < 0 || f >= ICAR_N_FIELDS || field_is_2dd(f) || f == ICAR_F_TERRAIN || f == ICAR_F_LAND_MASK) { icar_set_error("dqdt_upload: bad field"); return 1; }
     const size_t bytes = icar_field_count(c, f) * sizeof(float);
     if (!c->dqdt[f]) HIPCHK(hipMalloc(&c->dqdt[f], bytes));
     HIPCHK(hipMemcpyAsync(c->dqdt[f], host, bytes, hipMemcpyHostToDevice, c->stream));
@@ -701,6 +705,20 @@ int icar_hip_wsm6_tiles(icar_hip_ctx *c, float dt, int ntiles, const int tiles[]
 }
 
 int icar_hip_winds_valid(icar_hip_ctx *c) { return (c && c->winds_valid) ? 1 : 0; }
+
+int icar_hip_pbl_simple(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte)
+{
+    if (!c) { icar_set_error("null ctx"); return 1; }
+    HIPCHK(hipSetDevice(c->device));
+    return icar_pbl_simple_run(c, dt, its, ite, jts, jte, kts, kte);
+}
+
+int icar_hip_pbl_nsubsteps(icar_hip_ctx *c, int *nsubsteps, int nrows)
+{
+    if (!c || !nsubsteps) { icar_set_error("pbl_nsubsteps: null argument"); return 1; }
+    HIPCHK(hipSetDevice(c->device));
+    return icar_pbl_nsubsteps_copy(c, nsubsteps, nrows);
+}
 
 int icar_hip_wsm6_init(icar_hip_ctx *c)
 {

@@ -41,6 +41,7 @@ struct IcarStepState {
     bool early_open = false, early_wreal = false, early_face = false;   // a sub-step whose dt-independent opening is already in flight
     bool failed = false;                 // a sub-step was abandoned half-applied (timestep.hip: update_dt_opened): the fields are not a model state any more
     bool winds_first = true;                 // wind.f90:297 `.not. allocated(domain%sintheta)`: update_winds has not run yet
+    int boundarylayer = 0;                   // options%physics%boundarylayer (icar_hip_pbl_configure): 0, 1 or ICAR_PBL_SIMPLE
 };
 
 // component indices of the per-cell coefficients in icar_hip_ctx::mpc (k_mpdata_coef in mpdata.hip says what they hold): the first
@@ -84,6 +85,8 @@ struct icar_hip_ctx {
     hipEvent_t cfl_ev = nullptr;
     float *iw_adj = nullptr;             // iterative_winds ADJ scratch (iterative_winds.hip)
     float *wgr_tmp = nullptr;            // make_winds_grid_relative: rotated mass-grid u | v (2 x n3)
+    float *pbl_kq = nullptr;             // pbl_simple.hip: Kq_m of the last call (n3), allocated on first use
+    unsigned *pbl_rowmax = nullptr;      // pbl_simple.hip: bit pattern of maxval(Kq/dz) of every row (ny)
     // reductions / flags
     float *d_red = nullptr;              // small device scratch for reductions
     std::vector<float> dzl_host;         // dz_levels last uploaded behind d_red (compute_dt re-sends them only when they change)
@@ -122,6 +125,9 @@ int icar_advect_setup_winds(icar_hip_ctx *c, int scheme, float dt, float dx, int
 int icar_advect_run(icar_hip_ctx *c, int scheme, int order, int fct, int advect_density, const int *fields, int n);
 int icar_mp_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte, int *err);
 int icar_mp_simple_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int tiles[][4], int kts, int kte, int *err);
+int icar_pbl_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);
+int icar_pbl_run(icar_hip_ctx *c, float dt);                                // pbl(domain, options, dt): the configured scheme on the step's tile
+int icar_pbl_nsubsteps_copy(icar_hip_ctx *c, int *out, int n);
 int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset);      // halo / subset < 0: argument not present
 int icar_update_dt(icar_hip_ctx *c, double *seconds);
 int icar_substep(icar_hip_ctx *c, double dt, bool enforce);

@@ -7,6 +7,7 @@
 // What runs beside what (same launches, operands and results as the plain sequence):
 //   main stream (the critical path)                       second stream (side work, done before each join)
 //   diagnostic_update part 1 (exner, T, rho, ...)
+//   [pbl, when icar_hip_pbl_configure switched it on: it reads u_mass / v_mass, so the whole of part 1 runs in front of it]
 //   mp(subset=1) interior                                 mp(halo=1) strips -> halo_send (pack + RCCL)   time_step.f90:512-526
 //   |                                                     setup_module_winds (+ MPDATA coefficients) of the advect() that follows
 //   halo_retrieve (unpack)  <----------------------------- join
@@ -195,6 +196,7 @@ struct AuxScope {          // entry points called while this object lives launch
 bool icar_substep_can_open_early(icar_hip_ctx *c)
 {
     const icar_hip_step_config &g = c->step.cfg;
+    if (c->step.boundarylayer == ICAR_PBL_SIMPLE) return false;                   // pbl(domain, options, dt) opens the sub-step and takes dt
     return g.microphysics != 0 && g.halo_size == 1 && g.mp_update_interval == 0.0f && c->step.mp_last_model_time != -999.0
         && g.prefetch_dt && (g.cfl_strictness == 3 || g.cfl_strictness == 4) && icar_cfl_prefetch_waiting(c) && !c->on_aux;
 }
@@ -260,6 +262,7 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce)
     const float dtf = (float)dt;
     const bool adv = (g.advection == ICAR_ADV_UPWIND || g.advection == ICAR_ADV_MPDATA);
     const bool stepping = dt > 1e-3;                                              // :483
+    const bool pbl = c->step.boundarylayer == ICAR_PBL_SIMPLE;
     bool wreal_later = false, face_later = false, wreal_done = false;
     const bool early = c->step.early_open;
     c->step.early_open = false;
@@ -278,13 +281,14 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce)
         if (g.microphysics != kMP_WSM3) {                                         // WSM3 reads w_real
             // exner / T / density now; the interface values and mass-point winds (nothing the microphysics reads or writes)
             // beside the interior launch below
-            face_later = stepping && g.microphysics != 0;
+            face_later = stepping && g.microphysics != 0 && !pbl;                 // (simple_pbl reads u_mass and v_mass: nothing of part 1 can wait)
             if (icar_diagnostic_update_run(c, face_later ? ICAR_DIAG_CELL : 1)) return 1;
             if (stepping) wreal_later = true;                                     // beside the advection, below
             else if (icar_diagnostic_update_run(c, 2)) return 1;
         } else if (icar_diagnostic_update_run(c, 3)) return 1;
     }
     if (!stepping) return 0;
+    if (pbl && icar_pbl_run(c, dtf)) return 1;                                    // :494 pbl(domain, options, real(dt%seconds()))
 
     // :512-526  mp(halo=1) -> halo_send -> mp(subset=1) -> halo_retrieve
     if (early) {
@@ -443,6 +447,24 @@ int icar_hip_step_configure(icar_hip_ctx *c, const icar_hip_step_config *cfg, co
 int icar_hip_model_time_set(icar_hip_ctx *c, double seconds) { if (!c) { icar_set_error("null ctx"); return 1; } c->step.model_time = seconds; c->step.failed = false; return 0; }
 double icar_hip_model_time(const icar_hip_ctx *c) { return c ? c->step.model_time : 0.0; }
 int icar_hip_mp_reset(icar_hip_ctx *c) { if (!c) { icar_set_error("null ctx"); return 1; } c->step.mp_last_model_time = -999.0; return 0; }
+
+int icar_hip_pbl_configure(icar_hip_ctx *c, int boundarylayer)
+{
+    // the value is looked at first: a host learns that YSU is not built without a device
+    if (boundarylayer == 3) { icar_set_error("pbl_configure: boundarylayer = 3 (kPBL_YSU) is not built; 0, 1 (kPBL_BASIC, nothing runs) or 2 (kPBL_SIMPLE)"); return 1; }
+    if (boundarylayer < 0 || boundarylayer > 3) { icar_set_error("pbl_configure: boundarylayer is 0, 1 (kPBL_BASIC, nothing runs) or 2 (kPBL_SIMPLE)"); return 1; }
+    if (!c) { icar_set_error("pbl_configure: null ctx"); return 1; }
+    c->step.boundarylayer = boundarylayer;
+    return 0;
+}
+
+int icar_hip_pbl(icar_hip_ctx *c, float dt)
+{
+    if (!c) { icar_set_error("null ctx"); return 1; }
+    if (!cfg_ok(c, "pbl")) return 1;
+    HIPCHK(hipSetDevice(c->device));
+    return icar_pbl_run(c, dt);
+}
 
 int icar_hip_mp(icar_hip_ctx *c, double dt, int halo, int subset)
 {

@@ -30,6 +30,7 @@ class domain_t:
         self.device = int(device)
         self.exchange_vars = []          # kVARS names with an associated exchangeable (halo_send order)
         self._step_key = None            # what the library's step driver was last configured with (configure())
+        self._pbl_key = 0                # options%physics%boundarylayer as last handed to icar_hip_pbl_configure
         self._forced, self._diagnostics, self._prefetch_dt = (), True, True
         if comm is not None:
             comm.attach(self)            # icar_hip_comm_init[_host]: collective over the images of the communicator
@@ -50,13 +51,18 @@ class domain_t:
     def model_time_seconds(self, seconds):
         check(lib().icar_hip_model_time_set(self.ctx, float(seconds)), "icar_hip_model_time_set")
 
-    def configure(self, options, forced=None, diagnostics=None, prefetch_dt=None, advection=None):
+    def configure(self, options, forced=None, diagnostics=None, prefetch_dt=None, advection=None, boundarylayer=None):
         """icar_hip_step_configure: hand the library the members of options_t / grid_t that step(), update_dt(), mp() and
         advect() read (time_step.f90:440-551).  Cheap when nothing changed.  forced = [(member, force_boundaries), ...] (the
         variables apply_forcing updates), diagnostics (diagnostic_update at the top of a sub-step) and prefetch_dt stay as last
         given when omitted.  advection=0 overrides options%physics%advection (time_step.mp_and_halo: the microphysics + halo
-        block alone)."""
+        block alone), boundarylayer=0 likewise options%physics%boundarylayer (handed to icar_hip_pbl_configure: pbl() then runs
+        between diagnostic_update and the microphysics of every sub-step)."""
         p, g = options.parameters, self.grid
+        bl = int(options.physics.boundarylayer if boundarylayer is None else boundarylayer)
+        if bl != self._pbl_key:
+            check(lib().icar_hip_pbl_configure(self.ctx, bl), "icar_hip_pbl_configure")
+            self._pbl_key = bl
         adv = options.physics.advection if advection is None else advection
         adv_ids = tuple(KVARS[n][0] for n in ADVECTION_ORDER if options.vars_to_advect.get(n, 0) > 0)
         if forced is not None: self._forced = tuple((self.fid(n), int(bool(b))) for n, b in forced)
@@ -109,7 +115,7 @@ class domain_t:
     def shape(self, fid):
         if fid in (F.U, F.JACOBIAN_U, F.DZDX, F.ZR_U): return (self.ny, self.nz, self.nx + 1)
         if fid in (F.V, F.JACOBIAN_V, F.DZDY, F.ZR_V): return (self.ny + 1, self.nz, self.nx)
-        if fid in F.IS_2DD or fid in (F.SURFACE_PRESSURE, F.IVT, F.IWV, F.IWL, F.IWI): return (self.ny, self.nx)
+        if fid in F.IS_2DD or fid in (F.SURFACE_PRESSURE, F.IVT, F.IWV, F.IWL, F.IWI, F.TERRAIN, F.LAND_MASK): return (self.ny, self.nx)
         return (self.ny, self.nz, self.nx)
 
     @staticmethod
@@ -122,7 +128,7 @@ class domain_t:
     def set(self, name, array):
         """Upload a host array (C-order (ny,nz,nx) == Fortran (i,k,j)) into the named member."""
         fid = self.fid(name)
-        dt = np.float64 if fid in F.IS_2DD else np.float32
+        dt = np.float64 if fid in F.IS_2DD else np.int32 if fid in F.IS_2DI else np.float32
         a = np.ascontiguousarray(array, dtype=dt)
         if a.shape != self.shape(fid):
             raise ValueError(f"{name}: shape {a.shape} != {self.shape(fid)}")
@@ -132,7 +138,7 @@ class domain_t:
 
     def get(self, name):
         fid = self.fid(name)
-        a = np.empty(self.shape(fid), np.float64 if fid in F.IS_2DD else np.float32)
+        a = np.empty(self.shape(fid), np.float64 if fid in F.IS_2DD else np.int32 if fid in F.IS_2DI else np.float32)
         check(lib().icar_hip_field_download(self.ctx, fid, a.ctypes.data_as(ctypes.c_void_p)), f"download {name}")
         return a
 
@@ -223,7 +229,8 @@ class domain_t:
         return not (getattr(self, "_stream_ptr", 0) and self._stream_ptr == cur)
 
     def load_case(self, case):
-        """Upload every member present in an icar_amd.ideal case dict."""
+        """Upload every member present in an icar_amd.ideal case dict (terrain and, when the case has one, land_mask included:
+        simple_pbl reads them; without a land_mask every cell is land)."""
         alias = {"cloud_water": "cloud_water_mass", "rain": "rain_mass", "snow": "snow_mass",
                  "cloud_ice": "cloud_ice_mass", "graupel": "graupel_mass", "ice_number": "cloud_ice_number"}
         for k, v in case.items():

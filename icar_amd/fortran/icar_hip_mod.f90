@@ -11,7 +11,7 @@ module icar_hip
   use iso_c_binding
   implicit none
   private
-  public :: hip_ctx_t, hip_create, hip_destroy, hip_upload, hip_download, hip_upload_2dd, hip_download_2dd, &
+  public :: hip_ctx_t, hip_create, hip_destroy, hip_upload, hip_download, hip_upload_2dd, hip_download_2dd, hip_upload_2d, hip_upload_2di, &
             hip_advect, hip_mp_simple, hip_thompson_init, hip_thompson, hip_max_courant, hip_balance_uvw, hip_sync, &
             hip_lt_options_t, hip_setup_linwinds, hip_linwinds_build_lut, hip_spatial_winds, hip_iterative_winds, &
             hip_iterative_winds_correct_w, hip_iterative_winds_sweep, &
@@ -20,14 +20,16 @@ module icar_hip
             hip_aux_fork, hip_aux_begin, hip_aux_end, hip_aux_join, hip_max_courant_device, hip_make_winds_grid_relative, &
             hip_step_config_t, hip_step_configure, hip_update_dt, hip_compute_dt, hip_substep, hip_step, hip_step_n, hip_mp, hip_advect_step, hip_mp_reset, &
             hip_model_time, hip_set_model_time, hip_comm_unique_id, hip_comm_init, hip_comm_init_local, hip_comm_init_host, hip_comm_destroy, &
-            hip_halo_send, hip_halo_retrieve, hip_co_min, hip_comm_ranks, hip_halo_selfcheck, hip_update_winds, hip_exchange_uv, hip_mpdata_exact, ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_SELF, ICAR_N_ADVECTABLE
+            hip_halo_send, hip_halo_retrieve, hip_co_min, hip_comm_ranks, hip_halo_selfcheck, hip_update_winds, hip_exchange_uv, hip_mpdata_exact, &
+            hip_pbl_configure, hip_pbl, hip_pbl_simple, ICAR_PBL_SIMPLE, ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_SELF, ICAR_N_ADVECTABLE
   public :: ICAR_F_WATER_VAPOR, ICAR_F_CLOUD_WATER, ICAR_F_RAIN, ICAR_F_SNOW, ICAR_F_POTENTIAL_TEMPERATURE, &
             ICAR_F_CLOUD_ICE, ICAR_F_GRAUPEL, ICAR_F_ICE_NUMBER, ICAR_F_RAIN_NUMBER, ICAR_F_U, ICAR_F_V, ICAR_F_W, &
             ICAR_F_PRESSURE, ICAR_F_EXNER, ICAR_F_DENSITY, ICAR_F_DZ_MASS, ICAR_F_JACOBIAN, ICAR_F_JACOBIAN_U, &
             ICAR_F_JACOBIAN_V, ICAR_F_JACOBIAN_W, ICAR_F_ADVECTION_DZ, ICAR_F_PRECIPITATION, ICAR_F_SNOWFALL, ICAR_F_GRAUPEL_ACC, &
             ICAR_F_Z, ICAR_F_NSQUARED, ICAR_F_PRESSURE_INTERFACE, ICAR_F_TEMPERATURE, ICAR_F_TEMPERATURE_INTERFACE, &
             ICAR_F_U_MASS, ICAR_F_V_MASS, ICAR_F_W_REAL, ICAR_F_DZDX, ICAR_F_DZDY, ICAR_F_SURFACE_PRESSURE, &
-            ICAR_F_IVT, ICAR_F_IWV, ICAR_F_IWL, ICAR_F_IWI, ICAR_F_ZR_U, ICAR_F_ZR_V, ICAR_F_SINTHETA, ICAR_F_COSTHETA
+            ICAR_F_IVT, ICAR_F_IWV, ICAR_F_IWL, ICAR_F_IWI, ICAR_F_ZR_U, ICAR_F_ZR_V, ICAR_F_SINTHETA, ICAR_F_COSTHETA, &
+            ICAR_F_TERRAIN, ICAR_F_LAND_MASK
 
   ! enum icar_hip_field (include/icar_hip.h)
   integer(c_int), parameter :: ICAR_F_WATER_VAPOR=0, ICAR_F_CLOUD_WATER=1, ICAR_F_RAIN=2, ICAR_F_SNOW=3, &
@@ -37,9 +39,10 @@ module icar_hip
        ICAR_F_PRECIPITATION=23, ICAR_F_SNOWFALL=24, ICAR_F_GRAUPEL_ACC=25, ICAR_F_PRESSURE_INTERFACE=26, ICAR_F_TEMPERATURE=27, &
        ICAR_F_TEMPERATURE_INTERFACE=28, ICAR_F_U_MASS=29, ICAR_F_V_MASS=30, ICAR_F_W_REAL=31, ICAR_F_DZDX=32, ICAR_F_DZDY=33, &
        ICAR_F_SURFACE_PRESSURE=34, ICAR_F_Z=35, ICAR_F_NSQUARED=36, ICAR_F_IVT=37, ICAR_F_IWV=38, ICAR_F_IWL=39, ICAR_F_IWI=40, &
-       ICAR_F_ZR_U=41, ICAR_F_ZR_V=42, ICAR_F_SINTHETA=43, ICAR_F_COSTHETA=44
+       ICAR_F_ZR_U=41, ICAR_F_ZR_V=42, ICAR_F_SINTHETA=43, ICAR_F_COSTHETA=44, ICAR_F_TERRAIN=45, ICAR_F_LAND_MASK=46
 
   integer(c_int), parameter :: ICAR_N_ADVECTABLE = 11, ICAR_NEIGHBOR_NONE = -1, ICAR_NEIGHBOR_SELF = -2
+  integer(c_int), parameter :: ICAR_PBL_SIMPLE = 2      ! kPBL_SIMPLE, icar_constants.f90:355
 
   !> struct icar_hip_step_config == the members of options_t / grid_t the sub-step loop reads (time_step.f90:440-551)
   type, bind(C) :: hip_step_config_t
@@ -131,6 +134,15 @@ module icar_hip
      end function
      integer(c_int) function icar_hip_winds_valid(ctx) bind(C, name="icar_hip_winds_valid")
        import; type(c_ptr), value :: ctx
+     end function
+     integer(c_int) function icar_hip_pbl_simple(ctx, dt, its, ite, jts, jte, kts, kte) bind(C, name="icar_hip_pbl_simple")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt; integer(c_int), value :: its, ite, jts, jte, kts, kte
+     end function
+     integer(c_int) function icar_hip_pbl_configure(ctx, boundarylayer) bind(C, name="icar_hip_pbl_configure")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: boundarylayer
+     end function
+     integer(c_int) function icar_hip_pbl(ctx, dt) bind(C, name="icar_hip_pbl")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt
      end function
      integer(c_int) function icar_hip_wsm6_init(ctx) bind(C, name="icar_hip_wsm6_init")
        import; type(c_ptr), value :: ctx
@@ -355,6 +367,29 @@ contains
     call check(icar_hip_advect_step(ctx%p, dt), "advect_step")
   end subroutine
 
+  !> options%physics%boundarylayer for the sub-step loop: 0, 1 (kPBL_BASIC: nothing runs) or ICAR_PBL_SIMPLE; 3 (YSU) stops
+  subroutine hip_pbl_configure(ctx, boundarylayer)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer, intent(in) :: boundarylayer
+    call check(icar_hip_pbl_configure(ctx%p, int(boundarylayer,c_int)), "pbl_configure")
+  end subroutine
+
+  !> pbl(domain, options, dt) (pbl_driver.f90:197-221) on the tile of hip_step_configure; dt = real(dt%seconds())
+  subroutine hip_pbl(ctx, dt)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    call check(icar_hip_pbl(ctx%p, real(dt,c_float)), "pbl")
+  end subroutine
+
+  !> simple_pbl (pbl_simple.f90:69-141) on the context's fields; ICAR_F_TERRAIN and (optionally) ICAR_F_LAND_MASK uploaded once
+  subroutine hip_pbl_simple(ctx, dt, its, ite, jts, jte, kts, kte)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    integer, intent(in) :: its, ite, jts, jte, kts, kte
+    call check(icar_hip_pbl_simple(ctx%p, real(dt,c_float), int(its,c_int), int(ite,c_int), int(jts,c_int), int(jte,c_int), &
+                                   int(kts,c_int), int(kte,c_int)), "pbl_simple")
+  end subroutine
+
   subroutine hip_mp_reset(ctx)
     type(hip_ctx_t), intent(in) :: ctx
     call check(icar_hip_mp_reset(ctx%p), "mp_reset")
@@ -553,6 +588,21 @@ contains
     integer(c_int), intent(in) :: field
     real(c_double), intent(inout), target, contiguous :: a(:,:)
     call check(icar_hip_field_download(ctx%p, field, c_loc(a)), "field_download")
+  end subroutine
+
+  !> domain%terrain%data_2d (REAL(4)) and domain%land_mask (INTEGER) -> ICAR_F_TERRAIN / ICAR_F_LAND_MASK, what simple_pbl reads
+  subroutine hip_upload_2d(ctx, field, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: field
+    real(c_float), intent(in), target, contiguous :: a(:,:)
+    call check(icar_hip_field_upload(ctx%p, field, c_loc(a)), "field_upload")
+  end subroutine
+
+  subroutine hip_upload_2di(ctx, field, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: field
+    integer(c_int), intent(in), target, contiguous :: a(:,:)
+    call check(icar_hip_field_upload(ctx%p, field, c_loc(a)), "field_upload")
   end subroutine
 
   !> advect(domain, options, dt) of advection_driver.f90:51 : scheme = options%physics%advection,

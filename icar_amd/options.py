@@ -10,6 +10,8 @@ class physics_type:                      # opt_types.f90:15-24
     microphysics: int = 0
     advection: int = kADV_MPDATA
     windtype: int = 0
+    boundarylayer: int = 0               # 0, kPBL_BASIC (nothing runs), kPBL_SIMPLE (icar_amd.pbl)
+    landsurface: int = 0                 # (read by pbl_var_request only, as in the reference)
 
 
 @dataclass

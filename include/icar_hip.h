@@ -83,7 +83,10 @@ enum icar_hip_field {
     /* make_winds_grid_relative (src/physics/wind.f90:236-287): domain%sintheta / costheta, REAL(8) (nx,ny) */
     ICAR_F_SINTHETA = 43,
     ICAR_F_COSTHETA = 44,
-    ICAR_N_FIELDS = 45
+    /* simple_pbl (src/physics/pbl_simple.f90:69-86): read-only surface description, uploaded once */
+    ICAR_F_TERRAIN = 45,           /* domain%terrain%data_2d  REAL(4) (nx,ny)    */
+    ICAR_F_LAND_MASK = 46,         /* domain%land_mask  INTEGER(4) (nx,ny): kLC_LAND = 1, kLC_WATER = 2 */
+    ICAR_N_FIELDS = 47
 };
 
 enum { ICAR_ADV_UPWIND = 1, ICAR_ADV_MPDATA = 2 };   /* kADV_UPWIND / kADV_MPDATA, icar_constants.f90:341 */
@@ -199,6 +202,28 @@ int icar_hip_wsm6(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, int jt
 /* process_halo's strips (src/physics/mp_driver.f90:609-658) in ONE sequence of launches over up to 4 non-overlapping tiles
  * {its,ite,jts,jte} (as icar_hip_mp_tiles returns them), like icar_hip_thompson_tiles / icar_hip_mp_simple_tiles */
 int icar_hip_wsm6_tiles(icar_hip_ctx *ctx, float dt, int ntiles, const int tiles[][4], int kts, int kte);
+
+/* ---- P1: the simple boundary-layer scheme (HP96; src/physics/pbl_simple.f90, src/physics/pbl_driver.f90) ----------------
+ * icar_hip_pbl_simple == simple_pbl(th, qv, cloud, ice, qrain, qsnow, u_mass, v_mass, exner, density, z, dz_mass, terrain,
+ *     land_mask, its, ite, jts, jte, kts, kte, dt) (pbl_simple.f90:69-141 with pbl_diffusion :165-211) on the context's
+ *     POTENTIAL_TEMPERATURE, WATER_VAPOR, CLOUD_WATER, CLOUD_ICE, RAIN, SNOW (mixed in place), U_MASS, V_MASS, EXNER, DENSITY, Z,
+ *     DZ_MASS, TERRAIN and LAND_MASK (never uploaded = all land).  Bit-identical to the compiled reference, including its
+ *     quirks: the explicit diffusion of a row j takes ceiling(2 maxval(Kq/dz)) sub-steps over its:ite of THAT CALL, so the
+ *     result depends on how a domain is cut into tiles; graupel and the number concentrations are not mixed; the level
+ *     kte+1 only receives the top flux; temperature and density are not re-diagnosed.  kte is lowered to kme-1 (:92); a
+ *     call that leaves no half level (one level) is an error, and so are more than 1024 levels.
+ * icar_hip_pbl_configure: options%physics%boundarylayer -- 0, 1 (kPBL_BASIC: pbl_driver.f90 has no branch for it, nothing
+ *     runs) or ICAR_PBL_SIMPLE = kPBL_SIMPLE (icar_constants.f90:355); 3 (kPBL_YSU) is refused: not built.  With the scheme
+ *     configured icar_hip_substep / _step / _step_n call pbl between diagnostic_update and the microphysics
+ *     (time_step.f90:494) when dt > 1e-3 (:483).  Kept out of icar_hip_step_config so that the struct keeps its layout.
+ * icar_hip_pbl == pbl(domain, options, dt) (pbl_driver.f90:197-221) with the tile bounds of icar_hip_step_configure.
+ * icar_hip_pbl_nsubsteps: the sub-step count of every row jms..jme of the last call (0 outside its jts..jte), for tests and
+ *     measurements; no counterpart in the reference (a local of pbl_diffusion). */
+enum { ICAR_PBL_SIMPLE = 2 };
+int icar_hip_pbl_simple(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, int jte, int kts, int kte);
+int icar_hip_pbl_configure(icar_hip_ctx *ctx, int boundarylayer);
+int icar_hip_pbl(icar_hip_ctx *ctx, float dt);
+int icar_hip_pbl_nsubsteps(icar_hip_ctx *ctx, int *nsubsteps, int nrows);
 
 /* ---- T2: CFL reduction for compute_dt (src/main/time_step.f90:217-330, cfl_strictness 3) -----
  * out = max over the tile of max(|u_i|,|u_i+1|)/dx + max(|v_j|,|v_j+1|)/dx + max(|w_k|,|w_k-1|)/dz_levels(k) */
@@ -441,7 +466,7 @@ int icar_hip_step_n(icar_hip_ctx *ctx, int nsteps, double *dt_last);
 
 /* ---- measurement helpers --------------------------------------------------------------------- */
 /* Average duration (ms) of the launches of a named kernel group since the last reset, measured
- * with HIP events on the context's stream (bench.py roofline block). group: "advect", "mp". */
+ * with HIP events on the context's stream (bench.py roofline block). group: "advect", "mp", "pbl" ... */
 int icar_hip_timing_enable(icar_hip_ctx *ctx, int on);
 /* restrict the timers to a comma-separated list of groups ("advect", "advect,mp,winds"; NULL or "" = all): every timed
  * scope costs its stream two timestamped barrier packets, ~5 us -- a dozen groups per sub-step are 10 % of a small tile's step */
