@@ -3,7 +3,7 @@
  * wsm32D :218-903, rgmma :905-924, wsm3init :951-1006, slope_wsm3 :1008-1068, nislfv_rain_plm :1266-1504 -- written for this
  * checker only, from the Fortran.  It keeps the reference's own decomposition: one (i,k) SLAB per j row, every loop nest of
  * wsm32D a loop nest over the slab here, in the reference's order and REAL(4) operation order.  The product's device code
- * (icar_amd/csrc/wsm3_column.h + mp_wsm3.hip) is a separate text with a different decomposition (one column per lane, the
+ * (icar_amd/csrc/mp_wsm3.hip + wsm_fall.h) is a separate text with a different decomposition (one column per lane, the
  * levels marched in registers), so HIP == oracle is a comparison of two independent restatements.
  * PINNED by execution: tests/test_oracle_wsm3.py compares this file bit-for-bit with the unmodified mp_wsm3.f90 compiled into
  * oracle/_ref (the 42 constants of wsm3init and whole tiles over several steps).
