@@ -730,9 +730,7 @@ int icar_wsm6_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int tiles[]
     const dim3 gc((unsigned)((ncell + 255) / 256)), bc(256), g2((unsigned)((ncol + 63) / 64)), b2(64);
     const bool wave_falls = km + 1 <= 64;                       // lane = level; taller columns: one thread per column
     const dim3 gt(tl.boff[tl.n], 1, 1);
-    const size_t tile_lds = 8 * (size_t)km * (W6_TC + 1) * sizeof(float);
-    if (wave_falls && tile_lds > 64 * 1024)                     // more than 61 levels: above HIP's default dynamic-LDS limit (160 kB per CU on gfx950)
-        HIPCHK(hipFuncSetAttribute((const void *)k_w6_fall_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
+    const size_t tile_lds = 8 * (size_t)km * (W6_TC + 1) * sizeof(float);   // 544 km bytes: 34 272 at 63 levels, under the 64 kB a launch gets without asking
     if (wave_falls) hipLaunchKernelGGL(k_w6_zi, g2, b2, 0, c->stream, c->d, dz, W.zi, tl, k0, km);
     for (int loop = 1; loop <= loops; ++loop) {
         if (loop == 1) hipLaunchKernelGGL((k_w6_prep<true>), gc, bc, 0, c->stream, c->d, S->c, A, W, th, pii, q, qc, qi, qr, qs, qg, den, p, tl, k0, km);

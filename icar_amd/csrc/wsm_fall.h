@@ -216,16 +216,19 @@ __device__ __forceinline__ float wsm_wave_remap(int km, int lane, float zi, floa
     const float zlo = zi, zhi = wsm_dn(zi);                  // the output cell of this lane is [zi(lane), zi(lane+1)]
     const float za_top = __shfl(za, km);
     // arrival heights below zlo among interfaces 1..km (nb) and below zhi among 0..km-1 (nt): za increases strictly, so each
-    // count is the position of the first za >= z -- a 6-step binary search per lane instead of km+1 comparisons
-    int lo1 = 0, hi1 = km + 1, lo2 = 0, hi2 = km;
+    // count is the position of the first za >= z -- a 6-step binary search per lane instead of km+1 comparisons.  Both ranges hold
+    // km <= 63 interfaces: six halvings settle fewer than 64 candidates, not 64 (a search over 0..km left lane 0 of a 63-level
+    // column one candidate short whenever the lowest arrival height was below the ground and the next one above it).  The clamp of
+    // the probed lane to 63 acts only where lo1 == hi1 == 64 (km = 63, every candidate below zlo): a settled search, whose probe
+    // is read and discarded
+    int lo1 = 1, hi1 = km + 1, lo2 = 0, hi2 = km;
     for (int step = 0; step < 6; ++step) {
         const int m1 = (lo1 + hi1) >> 1, m2 = (lo2 + hi2) >> 1;
         const float v1 = __shfl(za, m1 < 63 ? m1 : 63), v2 = __shfl(za, m2 < 63 ? m2 : 63);
         if (lo1 < hi1) { if (v1 < zlo) lo1 = m1 + 1; else hi1 = m1; }
         if (lo2 < hi2) { if (v2 < zhi) lo2 = m2 + 1; else hi2 = m2; }
     }
-    const float za0 = __shfl(za, 0);
-    const int nb = lo1 - (za0 < zlo ? 1 : 0), nt = lo2;
+    const int nb = lo1 - 1, nt = lo2;
     const bool live = cell && !(zlo >= za_top);              // not yet `exit intp`
     const int kb = live ? nb + 1 : 1;                        // 1-based first kk with zi(k) <= za(kk+1); <= km when live
     const bool found = live && nt < km;                      // first kk with zi(k+1) <= za(kk) exists

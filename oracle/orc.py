@@ -310,3 +310,30 @@ def wsm6(th, q, qc, qr, qi, qs, qg, den, pii, p, delz, args18, rain, sr, snow, g
     fn = lib().orc_wsm6; fn.restype = ctypes.c_int
     return int(fn(_i(nx), _i(nz), _i(ny), _p(th), _p(q), _p(qc), _p(qr), _p(qi), _p(qs), _p(qg), _p(den), _p(pii), _p(p), _p(delz), _p(a),
                   _p(rain), _p(sr), _p(snow), _p(graupel), *[_i(x) for x in (its, ite, jts, jte, kts, kte)]))
+
+
+# ---- the semi-Lagrangian fall of WSM3 / WSM6 on its own (oracle/wsm6_oracle.c, oracle/wsm_fall_count.h) ---------------
+WSM_FALL_COUNTERS = ("empty columns lim_trip re_eval re_trip re_pass shaft_top exit_intp kt_eq_kb kt_gt_0mid kt_gt_mid max_mid kt_lt_kb "
+                     "rec_flat rec_sloped rec_clip out_none out_partial out_whole").split()
+
+
+def wsm_fall_counters(buf):
+    """buf = int64 (len(WSM_FALL_COUNTERS),): every following fall of wsm3(), wsm6() and wsm_fall_column() counts its branches
+    there (max_mid is a maximum, the others are sums); None switches the counting off.  The caller keeps buf alive."""
+    assert buf is None or (buf.dtype == np.int64 and buf.shape == (len(WSM_FALL_COUNTERS),) and buf.flags["C_CONTIGUOUS"])
+    lib().orc_wsm_fall_counters(ctypes.c_void_p(0) if buf is None else buf.ctypes.data_as(ctypes.c_void_p))
+
+
+def wsm_fall_column(den, denfac, tk, dz, ww, rql, dt, iter=1, speed=1):
+    """nislfv_rain_plm (rql of shape (1, km)) or nislfv_rain_plm6 ((2, km)) on one column; speed = 0 the scheme's own slopes
+    (after wsm6_init), 1 the probe speed of IEEE operations only.  Returns (fallen den*q of rql's shape, precip per field)."""
+    rql = np.ascontiguousarray(rql, np.float32).copy()
+    nf, km = rql.shape
+    a = [np.ascontiguousarray(x, np.float32) for x in (den, denfac, tk, dz, ww)]
+    assert all(x.shape == (km,) for x in a)
+    precip = np.zeros(nf, np.float32)
+    r2 = rql[1] if nf == 2 else None
+    fn = lib().orc_wsm_fall_column; fn.restype = ctypes.c_int
+    if fn(_i(km), _i(nf), _i(iter), _i(speed), *[_p(x) for x in a], _p(rql[0]), _p(r2), _f(dt), _p(precip)) != 0:
+        raise ValueError(f"wsm_fall_column: km = {km}, nf = {nf} not accepted")
+    return rql, precip

@@ -113,6 +113,7 @@ static void slope_wsm3(int n, const float *qrs, const float *den, const float *d
     }
 }
 
+#include "wsm_fall_count.h"
 #define MAXK 128
 /* nislfv_rain_plm :1266-1504: the semi-Lagrangian fall of den*q through the columns of one slab.  Slab arrays X(i,k) sit at
  * X[(k-1)*im + (i-1)]; the locals below are 1-based like the reference's (element 0 unused). */
@@ -131,7 +132,8 @@ static void nislfv_rain_plm(int im, int km, const float *denl, const float *denf
             dz[k] = dzl[c]; qq[k] = rql[c]; ww[k] = wwl[c]; den[k] = denl[c]; denfac[k] = denfacl[c]; tk[k] = tkl[c];
         }
         for (k = 1; k <= km; ++k) allold = allold + qq[k];
-        if (allold <= 0.0f) continue;                                       /* no precipitation in any layer */
+        if (allold <= 0.0f) { WFC(WFC_EMPTY); continue; }                   /* no precipitation in any layer */
+        WFC(WFC_COLUMNS);
         zi[1] = 0.0f;
         for (k = 1; k <= km; ++k) zi[k + 1] = zi[k] + dz[k];
         for (k = 1; k <= km; ++k) wd[k] = ww[k];                            /* departure wind */
@@ -144,10 +146,13 @@ static void nislfv_rain_plm(int im, int km, const float *denl, const float *denf
             for (k = 3; k <= km - 1; ++k) wi[k] = fa1 * (ww[k] + ww[k - 1]) - fa2 * (ww[k + 1] + ww[k - 2]);
             wi[km] = 0.5f * (ww[km] + ww[km - 1]);
             wi[km + 1] = ww[km];
-            for (k = 2; k <= km; ++k) if (ww[k] == 0.0f) wi[k] = ww[k - 1];  /* top of the rain group */
+            int changed = 0;                                                /* (counters only) wi[k + 1] was changed by the step before */
+            for (k = 2; k <= km; ++k) if (ww[k] == 0.0f) { wi[k] = ww[k - 1]; WFC(WFC_SHAFT_TOP); }  /* top of the rain group */
             for (k = km; k >= 1; --k) {                                     /* diffusivity of wi */
                 const float decfl = (wi[k + 1] - wi[k]) * dt / dz[k];
-                if (decfl > con1) wi[k] = wi[k + 1] - con1 * dz[k] / dt;
+                if (changed) WFC(WFC_RE_EVAL);
+                if (decfl > con1) { wi[k] = wi[k + 1] - con1 * dz[k] / dt; WFC(WFC_LIM_TRIP); if (changed) WFC(WFC_RE_TRIP); changed = 1; }
+                else { if (changed) WFC(WFC_RE_PASS); changed = 0; }
             }
             for (k = 1; k <= km + 1; ++k) za[k] = zi[k] - wi[k] * dt;       /* arrival points */
             for (k = 1; k <= km; ++k) dza[k] = za[k + 1] - za[k];
@@ -167,11 +172,12 @@ static void nislfv_rain_plm(int im, int km, const float *denl, const float *denf
             const float dip = (qa[k + 1] - qa[k]) / (dza[k + 1] + dza[k]);
             const float dim = (qa[k] - qa[k - 1]) / (dza[k - 1] + dza[k]);
             if (dip * dim <= 0.0f) {
-                qmi[k] = qa[k]; qpi[k] = qa[k];
+                qmi[k] = qa[k]; qpi[k] = qa[k]; WFC(WFC_REC_FLAT);
             } else {
                 qpi[k] = qa[k] + 0.5f * (dip + dim) * dza[k];
                 qmi[k] = 2.0f * qa[k] - qpi[k];
-                if (qpi[k] < 0.0f || qmi[k] < 0.0f) { qpi[k] = qa[k]; qmi[k] = qa[k]; }
+                if (qpi[k] < 0.0f || qmi[k] < 0.0f) { qpi[k] = qa[k]; qmi[k] = qa[k]; WFC(WFC_REC_CLIP); }
+                else WFC(WFC_REC_SLOPED);
             }
         }
         qpi[1] = qa[1]; qmi[1] = qa[1]; qmi[km + 1] = qa[km + 1]; qpi[km + 1] = qa[km + 1];
@@ -182,11 +188,13 @@ static void nislfv_rain_plm(int im, int km, const float *denl, const float *denf
             int kk, m;
             kb = kb - 1 > 1 ? kb - 1 : 1;
             kt = kt - 1 > 1 ? kt - 1 : 1;
-            if (zi[k] >= za[km + 1]) break;
+            if (zi[k] >= za[km + 1]) { WFC_ADD(WFC_EXIT_INTP, km - k + 1); break; }
             for (kk = kb; kk <= km; ++kk) if (zi[k] <= za[kk + 1]) { kb = kk; break; }
             for (kk = kt; kk <= km; ++kk) if (zi[k + 1] <= za[kk]) { kt = kk; break; }
             kt = kt - 1;
+            if (kt < kb) WFC(WFC_KT_LT_KB);
             if (kt == kb) {
+                WFC(WFC_KT_EQ_KB);
                 const float tl = (zi[k] - za[kb]) / dza[kb], th = (zi[k + 1] - za[kb]) / dza[kb];
                 const float tl2 = tl * tl, th2 = th * th;
                 const float qqd = 0.5f * (qpi[kb] - qmi[kb]);
@@ -201,6 +209,7 @@ static void nislfv_rain_plm(int im, int km, const float *denl, const float *denf
                 float zsum = (1.f - tl) * dza[kb];
                 float qsum = dql * dza[kb];
                 float th, th2, dqh;
+                if (kt - kb > 1) { WFC(WFC_KT_GT_MID); WFC_MAX(WFC_MAX_MID, kt - kb - 1); } else WFC(WFC_KT_GT_0MID);
                 if (kt - kb > 1) for (m = kb + 1; m <= kt - 1; ++m) { zsum = zsum + dza[m]; qsum = qsum + qa[m] * dza[m]; }
                 th = (zi[k + 1] - za[kt]) / dza[kt];
                 th2 = th * th;
@@ -212,11 +221,13 @@ static void nislfv_rain_plm(int im, int km, const float *denl, const float *denf
             }
         }
         /* rain out */
+        int whole = 0, part = 0;                                            /* (counters only) */
         for (k = 1; k <= km; ++k) {
-            if (za[k] < 0.0f && za[k + 1] < 0.0f) { precip[i] = precip[i] + qa[k] * dza[k]; continue; }
-            else if (za[k] < 0.0f && za[k + 1] >= 0.0f) { precip[i] = precip[i] + qa[k] * (0.0f - za[k]); break; }
+            if (za[k] < 0.0f && za[k + 1] < 0.0f) { precip[i] = precip[i] + qa[k] * dza[k]; ++whole; continue; }
+            else if (za[k] < 0.0f && za[k + 1] >= 0.0f) { precip[i] = precip[i] + qa[k] * (0.0f - za[k]); ++part; break; }
             break;
         }
+        WFC(whole ? WFC_OUT_WHOLE : part ? WFC_OUT_PARTIAL : WFC_OUT_NONE);
         for (k = 1; k <= km; ++k) rql[(size_t)(k - 1) * im + i] = qn[k];
     }
 }

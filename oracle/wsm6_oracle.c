@@ -12,6 +12,7 @@
  */
 #include <math.h>
 #include <stddef.h>
+#include "wsm_fall_count.h"
 extern int g_math_mode;
 static inline float x_exp(float x) { return g_math_mode ? (float)exp((double)x) : expf(x); }
 static inline float x_log(float x) { return g_math_mode ? (float)log((double)x) : logf(x); }
@@ -128,10 +129,13 @@ static void fall_arrival(int km, const float *ww, const float *dz, const float *
     for (int k = 2; k < km - 1; ++k) wi[k] = fa1 * (ww[k] + ww[k - 1]) - fa2 * (ww[k + 1] + ww[k - 2]);
     wi[km - 1] = 0.5f * (ww[km - 1] + ww[km - 2]);
     wi[km] = ww[km - 1];
-    for (int k = 1; k < km; ++k) if (ww[k] == 0.0f) wi[k] = ww[k - 1];
+    for (int k = 1; k < km; ++k) if (ww[k] == 0.0f) { wi[k] = ww[k - 1]; WFC(WFC_SHAFT_TOP); }
+    int changed = 0;                                         /* (counters only) wi[k + 1] was changed by the step before */
     for (int k = km - 1; k >= 0; --k) {
         const float decfl = (wi[k + 1] - wi[k]) * dt / dz[k];
-        if (decfl > con1) wi[k] = wi[k + 1] - con1 * dz[k] / dt;
+        if (changed) WFC(WFC_RE_EVAL);
+        if (decfl > con1) { wi[k] = wi[k + 1] - con1 * dz[k] / dt; WFC(WFC_LIM_TRIP); if (changed) WFC(WFC_RE_TRIP); changed = 1; }
+        else { if (changed) WFC(WFC_RE_PASS); changed = 0; }
     }
     for (int k = 0; k <= km; ++k) za[k] = zi[k] - wi[k] * dt;
     for (int k = 0; k < km; ++k) dza[k] = za[k + 1] - za[k];
@@ -145,11 +149,12 @@ static float fall_remap(int km, const float *zi, const float *za, const float *d
     for (int k = 1; k < km; ++k) {
         const float dip = (qa[k + 1] - qa[k]) / (dza[k + 1] + dza[k]);
         const float dim = (qa[k] - qa[k - 1]) / (dza[k - 1] + dza[k]);
-        if (dip * dim <= 0.0f) { qmi[k] = qa[k]; qpi[k] = qa[k]; }
+        if (dip * dim <= 0.0f) { qmi[k] = qa[k]; qpi[k] = qa[k]; WFC(WFC_REC_FLAT); }
         else {
             qpi[k] = qa[k] + 0.5f * (dip + dim) * dza[k];
             qmi[k] = 2.0f * qa[k] - qpi[k];
-            if (qpi[k] < 0.0f || qmi[k] < 0.0f) { qpi[k] = qa[k]; qmi[k] = qa[k]; }
+            if (qpi[k] < 0.0f || qmi[k] < 0.0f) { qpi[k] = qa[k]; qmi[k] = qa[k]; WFC(WFC_REC_CLIP); }
+            else WFC(WFC_REC_SLOPED);
         }
     }
     qpi[0] = qa[0]; qmi[0] = qa[0]; qmi[km] = qa[km]; qpi[km] = qa[km];
@@ -158,11 +163,13 @@ static float fall_remap(int km, const float *zi, const float *za, const float *d
     for (int k = 1; k <= km; ++k) {
         kb = kb - 1 > 1 ? kb - 1 : 1;
         kt = kt - 1 > 1 ? kt - 1 : 1;
-        if (zi[k - 1] >= za[km]) break;
+        if (zi[k - 1] >= za[km]) { WFC_ADD(WFC_EXIT_INTP, km - k + 1); break; }
         for (int kk = kb; kk <= km; ++kk) if (zi[k - 1] <= za[kk]) { kb = kk; break; }
         for (int kk = kt; kk <= km; ++kk) if (zi[k] <= za[kk - 1]) { kt = kk; break; }
         kt = kt - 1;
+        if (kt < kb) WFC(WFC_KT_LT_KB);
         if (kt == kb) {
+            WFC(WFC_KT_EQ_KB);
             const float tl = (zi[k - 1] - za[kb - 1]) / dza[kb - 1];
             const float th = (zi[k] - za[kb - 1]) / dza[kb - 1];
             const float tl2 = tl * tl, th2 = th * th;
@@ -171,6 +178,7 @@ static float fall_remap(int km, const float *zi, const float *za, const float *d
             const float qql = qqd * tl2 + qmi[kb - 1] * tl;
             qn[k - 1] = (qqh - qql) / (th - tl);
         } else if (kt > kb) {
+            if (kt - kb > 1) { WFC(WFC_KT_GT_MID); WFC_MAX(WFC_MAX_MID, kt - kb - 1); } else WFC(WFC_KT_GT_0MID);
             const float tl = (zi[k - 1] - za[kb - 1]) / dza[kb - 1];
             const float tl2 = tl * tl;
             float qqd = 0.5f * (qpi[kb - 1] - qmi[kb - 1]);
@@ -188,21 +196,33 @@ static float fall_remap(int km, const float *zi, const float *za, const float *d
             qn[k - 1] = qsum / zsum;
         }
     }
+    int whole = 0, part = 0;                                 /* (counters only) */
     for (int k = 0; k < km; ++k) {
-        if (za[k] < 0.0f && za[k + 1] < 0.0f) { precip = precip + qa[k] * dza[k]; continue; }
-        else if (za[k] < 0.0f && za[k + 1] >= 0.0f) { precip = precip + qa[k] * (0.0f - za[k]); break; }
+        if (za[k] < 0.0f && za[k + 1] < 0.0f) { precip = precip + qa[k] * dza[k]; ++whole; continue; }
+        else if (za[k] < 0.0f && za[k + 1] >= 0.0f) { precip = precip + qa[k] * (0.0f - za[k]); ++part; break; }
         break;
     }
+    WFC(whole ? WFC_OUT_WHOLE : part ? WFC_OUT_PARTIAL : WFC_OUT_NONE);
     return precip;
 }
 
 /* nislfv_rain_plm for one column: rql = den*q in / out; iter = 1 refines the fall speed once with slope_rain (rain), iter = 0 not (ice) */
-static float fall_plm(int km, const float *den, const float *denfac, const float *dz, const float *wwl, float *rql, float dt, int iter)
+/* the probe speed of tests/support/wsm_fall_probe.hip: +, *, / and sqrt only, so that a device kernel restates it exactly (no
+ * product feeds a sum: nothing to contract) */
+static float probe_speed(float q1, float q2, float den, float denfac, float tk)
+{
+    const float s = q1 + (q2 + q2);
+    return denfac * 60.f * sqrtf(sqrtf(s * den)) * (tk / 273.f);
+}
+
+static float fall_plm_s(int km, const float *den, const float *denfac, const float *tk, const float *dz, const float *wwl, float *rql, float dt,
+                        int iter, int speed)
 {
     float ww[MAXK], wi[MAXK + 1], zi[MAXK + 1], za[MAXK + 1], dza[MAXK + 1], qa[MAXK + 1], qn[MAXK];
     float allold = 0.0f;
     for (int k = 0; k < km; ++k) { ww[k] = wwl[k]; allold = allold + rql[k]; }
-    if (allold <= 0.0f) return 0.0f;
+    if (allold <= 0.0f) { WFC(WFC_EMPTY); return 0.0f; }
+    WFC(WFC_COLUMNS);
     zi[0] = 0.0f;
     for (int k = 0; k < km; ++k) zi[k + 1] = zi[k] + dz[k];
     for (int n = 1;; ++n) {
@@ -212,7 +232,7 @@ static float fall_plm(int km, const float *den, const float *denfac, const float
         if (n > iter) break;
         for (int k = 0; k < km; ++k) {
             float a, b, c, d;
-            const float wa = slope_r(qa[k] / den[k], den[k], denfac[k], &a, &b, &c, &d);
+            const float wa = speed ? probe_speed(qa[k] / den[k], 0.0f, den[k], denfac[k], tk[k]) : slope_r(qa[k] / den[k], den[k], denfac[k], &a, &b, &c, &d);
             ww[k] = 0.5f * (wwl[k] + wa);                     /* n == 1: no averaging with the previous estimate */
         }
     }
@@ -221,15 +241,21 @@ static float fall_plm(int km, const float *den, const float *denfac, const float
     return precip;
 }
 
+static float fall_plm(int km, const float *den, const float *denfac, const float *dz, const float *wwl, float *rql, float dt, int iter)
+{
+    return fall_plm_s(km, den, denfac, NULL, dz, wwl, rql, dt, iter, 0);      /* slope_rain reads no temperature */
+}
+
 /* nislfv_rain_plm6 for one column: snow (rql) and graupel (rql2) fall with ONE mass-weighted speed; iter = 1 */
-static void fall_plm6(int km, const float *den, const float *denfac, const float *tk, const float *dz, const float *wwl, float *rql, float *rql2,
-                      float dt, int iter, float *precip1, float *precip2)
+static void fall_plm6_s(int km, const float *den, const float *denfac, const float *tk, const float *dz, const float *wwl, float *rql, float *rql2,
+                        float dt, int iter, int speed, float *precip1, float *precip2)
 {
     float ww[MAXK], wi[MAXK + 1], zi[MAXK + 1], za[MAXK + 1], dza[MAXK + 1], qa[MAXK + 1], qa2[MAXK + 1], qn[MAXK];
     *precip1 = 0.0f; *precip2 = 0.0f;
     float allold = 0.0f;
     for (int k = 0; k < km; ++k) { ww[k] = wwl[k]; allold = allold + rql[k] + rql2[k]; }
-    if (allold <= 0.0f) return;
+    if (allold <= 0.0f) { WFC(WFC_EMPTY); return; }
+    WFC(WFC_COLUMNS);
     zi[0] = 0.0f;
     for (int k = 0; k < km; ++k) zi[k + 1] = zi[k] + dz[k];
     for (int n = 1;; ++n) {
@@ -240,6 +266,7 @@ static void fall_plm6(int km, const float *den, const float *denfac, const float
         for (int k = 0; k < km; ++k) {
             float a, b, c, d;
             const float qr = qa[k] / den[k], qr2 = qa2[k] / den[k];
+            if (speed) { ww[k] = 0.5f * (wwl[k] + probe_speed(qr, qr2, den[k], denfac[k], tk[k])); continue; }
             float wa = slope_s(qr, den[k], denfac[k], tk[k], &a, &b, &c, &d);
             const float wa2 = slope_g(qr2, den[k], denfac[k], &a, &b, &c, &d);
             const float tmp = fmx(qr + qr2, 1.E-15f);
@@ -252,6 +279,29 @@ static void fall_plm6(int km, const float *den, const float *denfac, const float
     *precip2 = fall_remap(km, zi, za, dza, qa2, qn);
     for (int k = 0; k < km; ++k) rql2[k] = qn[k];
 }
+
+static void fall_plm6(int km, const float *den, const float *denfac, const float *tk, const float *dz, const float *wwl, float *rql, float *rql2,
+                      float dt, int iter, float *precip1, float *precip2)
+{
+    fall_plm6_s(km, den, denfac, tk, dz, wwl, rql, rql2, dt, iter, 0, precip1, precip2);
+}
+
+/* ---- the fall of ONE column on its own (tests/test_gpu_wsm_fall.py, tests/test_wsm_columns_inputs.py) ----
+ * nf = 1: nislfv_rain_plm on rql1; nf = 2: nislfv_rain_plm6 on rql1 + rql2.  speed = 0: the scheme's own slopes refine the speed
+ * (slope_rain; slope_snow + slope_graup, mass-weighted; needs orc_wsm6_init), 1: probe_speed.  rql in / out, precip[nf] out.
+ * Returns 1 for km outside 3 .. MAXK or nf outside 1 .. 2. */
+int orc_wsm_fall_column(int km, int nf, int iter, int speed, const float *den, const float *denfac, const float *tk, const float *dz,
+                        const float *wwl, float *rql1, float *rql2, float dt, float *precip)
+{
+    if (km < 3 || km > MAXK || nf < 1 || nf > 2 || (nf == 2 && !rql2)) return 1;
+    if (nf == 1) precip[0] = fall_plm_s(km, den, denfac, tk, dz, wwl, rql1, dt, iter, speed);
+    else fall_plm6_s(km, den, denfac, tk, dz, wwl, rql1, rql2, dt, iter, speed, &precip[0], &precip[1]);
+    return 0;
+}
+
+/* counters of every fall that follows (wsm_fall_count.h; WSM3's and WSM6's alike), NULL = off.  The caller keeps buf alive. */
+long long *g_wsm_fall_cnt = NULL;
+void orc_wsm_fall_counters(long long *buf) { g_wsm_fall_cnt = buf; }
 
 /* statement functions of wsm62D :352-366 */
 #define CPMCAL(x) (A->cpd * (1.f - fmx(x, A->qmin)) + fmx(x, A->qmin) * A->cpv)

@@ -20,6 +20,12 @@ CASES = {"wsm3_warm_two_loops_26x14x24": dict(scheme=3, nx=26, ny=14, nz=24, ste
          "wsm3_snow_crossing_0C_24x12x30": dict(scheme=3, nx=24, ny=12, nz=30, steps=9, dt=75.0, moist=1.4, cool0=22.0, cool=1.0, seed=32),
          "wsm6_mixed_phase_24x12x30": dict(scheme=6, nx=24, ny=12, nz=30, steps=10, dt=75.0, moist=2.0, cool0=8.0, cool=1.5, seed=33),
          "wsm6_cold_two_loops_22x10x28": dict(scheme=6, nx=22, ny=10, nz=28, steps=5, dt=200.0, moist=1.3, cool0=35.0, cool=0.3, seed=34)}
+# the column-height sweep's own inputs (tests/wsm_columns_case.py) on a tile of COLUMNS_NX x 5 columns at the ends of the accepted
+# range and around the switch between the wave form and the serial form of the device's fall: three calls at the sweep's time step
+COLUMNS_NX = 21
+COLUMN_CASES = {f"wsm{s}_columns_{nz}_{st}": dict(scheme=s, nz=nz, state=st)
+                for s, nz, st in [(3, 3, "cold"), (6, 4, "cold"), (3, 41, "warm"), (6, 41, "cold"), (3, 62, "cold"), (6, 62, "warm"),
+                                  (3, 63, "warm"), (6, 63, "cold"), (3, 64, "cold"), (6, 64, "warm")]}
 K3 = ["potential_temperature", "water_vapor", "cloud_water", "rain"]
 K6 = K3 + ["cloud_ice", "snow", "graupel"]
 
@@ -83,6 +89,23 @@ def run_case(name):
     print("wrote", name, {n: float(A[n].max()) for n in keys[2:]}, "rain", float(out["acc_rain"].max()), "snow", float(out["acc_snow"].max()))
 
 
+def columns_fingerprint(c, scheme):
+    import wsm_columns_case as W
+    return float(sum(float(np.asarray(c[k], np.float64).sum()) for k in W.KEYS[scheme] + ["w_real", "density", "exner", "pressure", "dz_mass"]))
+
+
+def run_columns_case(name):
+    from oracle import ref
+    import wsm_columns_case as W
+    p = COLUMN_CASES[name]
+    ref.wsm3_init(); ref.wsm6_init()
+    c = W.make_case(p["scheme"], p["nz"], p["state"], nx=COLUMNS_NX)
+    out = W.oracle_run(None, p["scheme"], c, W.wsm_dt(p["nz"]), state=p["state"], ref=ref)
+    np.savez_compressed(os.path.join(HERE, name + ".npz"), params=np.array(json.dumps(p)),
+                        input_fingerprint=np.float64(columns_fingerprint(c, p["scheme"])), **out)
+    print("wrote", name, {k: float(v.max()) for k, v in out.items() if k.startswith("acc_")})
+
+
 if __name__ == "__main__":
-    for n in (sys.argv[1:] or CASES):
-        run_case(n)
+    for n in (sys.argv[1:] or list(CASES) + list(COLUMN_CASES)):
+        (run_case if n in CASES else run_columns_case)(n)

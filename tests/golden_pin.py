@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE.  The evidence chain of a `-m gpu` session is  HIP == oracle (liboracle.so as built on THAT box)  and
 oracle == tests/golden/*.npz (vectors written by the reference's own compiled kernels, tests/golden/make_golden*.py).  The tests
-that hold the second link (test_oracle_golden.py, test_oracle_thompson.py, test_oracle_wsm_golden.py, test_oracle_helpers_golden.py,
+that hold the second link (test_oracle_golden.py, test_oracle_thompson.py, test_oracle_wsm_golden.py, test_oracle_wsm_columns.py, test_oracle_helpers_golden.py,
 test_grid.py) are CPU tests and are not selected by `-m gpu`, so on the GPU box the freshly compiled oracle would go unpinned
 (VERDICT r05, weak #2).  pin() runs exactly those tests' bodies on the oracle the session is about to use -- the `oracle` fixture
 calls it before handing the oracle to the first device comparison, and any differing bit fails every test that takes the fixture.
@@ -31,6 +31,9 @@ def pin(orc):
     T.test_non_default_mp_options_tables_and_columns(orc)    # (leaves the default tables behind)
     for name in Wg.G.CASES:
         Wg.test_wsm_golden(orc, name)
+    import test_oracle_wsm_columns as Wc
+    for name in Wc.G.COLUMN_CASES:
+        Wc.test_wsm_columns_golden(orc, name)                # WSM3 / WSM6 at 3 / 4, 41, 62, 63 and 64 levels
     H.test_helpers_golden(orc)
     Gr.test_grid_matches_reference_golden(); util.COUNTS["bit_exact_fields"] += 1
     n = util.COUNTS["bit_exact_fields"] - n0
