@@ -491,22 +491,19 @@ int icar_hip_comm_destroy(icar_hip_ctx *c)
 
 int icar_hip_halo_send(icar_hip_ctx *c, int halo, const int *fields, int nfields)
 {
-    if (!c || (nfields > 0 && !fields)) { icar_set_error("halo_send: null argument"); return 1; }
-    HIPCHK(hipSetDevice(c->device));
+    if (icar_enter(c, "halo_send", fields || nfields <= 0)) return 1;
     return icar_comm_halo_send(c, halo, fields, nfields);
 }
 
 int icar_hip_halo_retrieve(icar_hip_ctx *c, int halo, const int *fields, int nfields)
 {
-    if (!c || (nfields > 0 && !fields)) { icar_set_error("halo_retrieve: null argument"); return 1; }
-    HIPCHK(hipSetDevice(c->device));
+    if (icar_enter(c, "halo_retrieve", fields || nfields <= 0)) return 1;
     return icar_comm_halo_retrieve(c, halo, fields, nfields);
 }
 
 int icar_hip_exchange_uv(icar_hip_ctx *c, int halo, int update)
 {
-    if (!c) { icar_set_error("exchange_uv: null ctx"); return 1; }
-    HIPCHK(hipSetDevice(c->device));
+    if (icar_enter(c, "exchange_uv")) return 1;
     const int r = icar_comm_exchange_uv(c, halo, update ? 1 : 0);
     if (!r && !update) icar_winds_changed(c);
     return r;
@@ -514,15 +511,13 @@ int icar_hip_exchange_uv(icar_hip_ctx *c, int halo, int update)
 
 int icar_hip_co_min(icar_hip_ctx *c, double *value)
 {
-    if (!c || !value) { icar_set_error("co_min: null argument"); return 1; }
-    HIPCHK(hipSetDevice(c->device));
+    if (icar_enter(c, "co_min", value != nullptr)) return 1;
     return icar_comm_co_reduce(c, value, true);
 }
 
 int icar_hip_co_max(icar_hip_ctx *c, double *value)
 {
-    if (!c || !value) { icar_set_error("co_max: null argument"); return 1; }
-    HIPCHK(hipSetDevice(c->device));
+    if (icar_enter(c, "co_max", value != nullptr)) return 1;
     return icar_comm_co_reduce(c, value, false);
 }
 

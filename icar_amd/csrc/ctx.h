@@ -120,35 +120,46 @@ struct ScopedTimer {
     ~ScopedTimer();
 };
 
-// kernels implemented in the .hip files
+// capi.hip: what every entry point that reaches the device does first: refuse a null context / pointer, select the context's device
+int icar_enter(icar_hip_ctx *c, const char *who, bool pointers_ok = true);
+inline void icar_winds_changed(icar_hip_ctx *c) { c->winds_valid = false; ++c->wind_version; }   // u, v, w (or density / jacobians) rewritten
+
+// the rows, under the file that defines them
+// advect.hip
 int icar_advect_setup_winds(icar_hip_ctx *c, int scheme, float dt, float dx, int advect_density, bool with_wreal = false, bool *wreal_done = nullptr);
 int icar_advect_run(icar_hip_ctx *c, int scheme, int order, int fct, int advect_density, const int *fields, int n);
+// mp_simple.hip
 int icar_mp_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte, int *err);
 int icar_mp_simple_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int tiles[][4], int kts, int kte, int *err);
+// pbl_simple.hip
 int icar_pbl_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);
 int icar_pbl_run(icar_hip_ctx *c, float dt);                                // pbl(domain, options, dt): the configured scheme on the step's tile
 int icar_pbl_nsubsteps_copy(icar_hip_ctx *c, int *out, int n);
+// timestep.hip
 int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset);      // halo / subset < 0: argument not present
 int icar_update_dt(icar_hip_ctx *c, double *seconds);
 int icar_substep(icar_hip_ctx *c, double dt, bool enforce);
-int icar_halo_pack(icar_hip_ctx *c, int dir, int halo, const int *fields, int n, float *buf, bool unpack);
+// halo_pack.hip
 int icar_halo_pack_dirs(icar_hip_ctx *c, int ndir, const int *dirs, int halo, const int *fields, int n, void *const *bufs, bool unpack);
+int icar_box_copy(icar_hip_ctx *c, int field, int which, int i0, int ni, int j0, int nj, float *buf, bool unpack);
+// cfl.hip
 int icar_max_courant_run(icar_hip_ctx *c, float dx, const float *dz_levels, float *out, float *d_out);
 int icar_max_abs_winds_run(icar_hip_ctx *c, float *out3);
+int icar_max_courant_prefetch_run(icar_hip_ctx *c, float dx, const float *dz_levels, bool allreduce);
+bool icar_cfl_prefetched_global(icar_hip_ctx *c, float dx, const float *dz_levels, float *value);
+bool icar_cfl_prefetch_waiting(icar_hip_ctx *c);      // a prefetched CFL maximum of the current winds is waiting for update_dt
+// iterative_winds.hip
 int icar_balance_uvw_run(icar_hip_ctx *c, float dx, int update);
 int icar_iterative_winds_correct_w(icar_hip_ctx *c, int update);
 int icar_mass_conservative_acceleration(icar_hip_ctx *c, int update);
 int icar_iterative_winds_sweep(icar_hip_ctx *c, float dx, int nsweeps, int update);
 int icar_make_winds_grid_relative(icar_hip_ctx *c, int update);
-int icar_box_copy(icar_hip_ctx *c, int field, int which, int i0, int ni, int j0, int nj, float *buf, bool unpack);
-enum { ICAR_DIAG_CELL = 4, ICAR_DIAG_FACE = 8 };     // finer parts of icar_diagnostic_update_run (step.hip), internal
+// step.hip
+enum { ICAR_DIAG_CELL = 4, ICAR_DIAG_FACE = 8 };     // finer parts of icar_diagnostic_update_run, internal
 int icar_diagnostic_update_run(icar_hip_ctx *c, int parts);
-int icar_max_courant_prefetch_run(icar_hip_ctx *c, float dx, const float *dz_levels, bool allreduce);
-bool icar_cfl_prefetched_global(icar_hip_ctx *c, float dx, const float *dz_levels, float *value);
-bool icar_cfl_prefetch_waiting(icar_hip_ctx *c);      // a prefetched CFL maximum of the current winds is waiting for update_dt
-inline void icar_winds_changed(icar_hip_ctx *c) { c->winds_valid = false; ++c->wind_version; }   // u, v, w (or density / jacobians) rewritten
 int icar_apply_forcing_run(icar_hip_ctx *c, double dt, const int *fields, const int *fb, int n, int w, int e, int s, int nn);
 int icar_enforce_limits_run(icar_hip_ctx *c, const int *fields, int n);
+// mp_thompson.hip, thompson_tables.hip
 int icar_thompson_init_run(icar_hip_ctx *c, const float *params, const int *flags);
 int icar_thompson_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte,
                       int ids, int ide, int jds, int jde, int kds, int kde);
@@ -156,7 +167,8 @@ int icar_thompson_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int (*t
                             int ids, int ide, int jds, int jde, int kds, int kde);
 int icar_thompson_prepare_constants(icar_hip_ctx *c);
 void icar_thompson_free(icar_hip_ctx *c);
-void icar_linwinds_free(icar_hip_ctx *c);
+int icar_thompson_table_download(icar_hip_ctx *c, const char *name, double *out, size_t cap, size_t *n_out);
+// mp_wsm3.hip, mp_wsm6.hip
 void icar_wsm3_free(icar_hip_ctx *c);
 int icar_wsm3_init_run(icar_hip_ctx *c);
 int icar_wsm3_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);
@@ -164,6 +176,8 @@ void icar_wsm6_free(icar_hip_ctx *c);
 int icar_wsm6_init_run(icar_hip_ctx *c);
 int icar_wsm6_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);
 int icar_wsm6_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int tiles[][4], int kts, int kte);
+// linear_winds.hip
+void icar_linwinds_free(icar_hip_ctx *c);
 int icar_linwinds_setup_run(icar_hip_ctx *c, const icar_hip_lt_options *o, const float *terrain, int nxg, int nyg, int ids, int jds, float dx);
 int icar_linear_perturbation_run(icar_hip_ctx *c, float U, float V, float Nsq, float zb, float zt, float minimum_step, double *u_out, double *v_out);
 int icar_linwinds_build_lut_run(icar_hip_ctx *c, const float *zb, const float *zt, int nlev);
@@ -173,4 +187,3 @@ int icar_linwinds_lut_entry(icar_hip_ctx *c, int comp, int k, int i, int j, floa
 int icar_linwinds_pert_copy(icar_hip_ctx *c, int comp, float *host, int to_dev);
 int icar_linwinds_terrain_frequency(icar_hip_ctx *c, double *out, size_t cap, int *fnx, int *fny);
 int icar_spatial_winds_run(icar_hip_ctx *c, int update);
-int icar_thompson_table_download(icar_hip_ctx *c, const char *name, double *out, size_t cap, size_t *n_out);

@@ -1,5 +1,6 @@
-// icar_amd/csrc/iterative_winds.hip -- SURVEY 8(f) rank 4: iterative_winds (src/physics/wind.f90:371-498)
-// and the staggered halo boxes its exchange_u / exchange_v need (src/objects/exchangeable_obj.f90:158-229).
+// icar_amd/csrc/iterative_winds.hip -- the device side of src/physics/wind.f90: balance_uvw (:81-169, row W1),
+// make_winds_grid_relative (:236-287), iterative_winds (:371-498) and mass_conservative_acceleration
+// (:500-511).  The staggered halo boxes that exchange_u / exchange_v move between the sweeps are packed in halo_pack.hip.
 //
 // The reference's loop body is three whole-array passes per iteration (calc_divergence, ADJ = div/ADJ_coef, four array
 // statements on u and v) followed by exchange_u/exchange_v.  Here one iteration is two streaming kernels:
@@ -70,18 +71,6 @@ __global__ void k_iw_apply(Dims d, float *__restrict__ u, float *__restrict__ v,
         x = x - a;
         v[c] = x;
     }
-}
-
-// box <-> contiguous buffer [nj][nz][ni]
-template <bool UNPACK>
-__global__ void k_box(int X, int nz, int i0, int ni, int j0, int nj, float *__restrict__ f, float *__restrict__ buf)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int k = blockIdx.y, jj = blockIdx.z;
-    if (t >= ni) return;
-    const size_t a = (size_t)(i0 + t) + (size_t)X * (k + (size_t)nz * (j0 + jj));
-    const size_t b = (size_t)t + (size_t)ni * (k + (size_t)nz * jj);
-    if (UNPACK) f[a] = buf[b]; else buf[b] = f[a];
 }
 
 __global__ void k_divide(size_t n, float *__restrict__ x, const float *__restrict__ a)
@@ -208,20 +197,48 @@ int icar_iterative_winds_sweep(icar_hip_ctx *c, float dx, int nsweeps, int updat
     return 0;
 }
 
-int icar_box_copy(icar_hip_ctx *c, int field, int which, int i0, int ni, int j0, int nj, float *buf, bool unpack)
+// ------------------------------------------------------------------------------------------------
+// W1: balance_uvw (wind.f90:81-169): w from the horizontal divergence, bottom-up per column
+// ------------------------------------------------------------------------------------------------
+__global__ void k_balance_uvw(Dims d, const float *__restrict__ u, const float *__restrict__ v, float *__restrict__ w,
+                              const float *__restrict__ ju, const float *__restrict__ jv, const float *__restrict__ jw,
+                              const float *__restrict__ dz, float dx)
 {
-    if (field < 0 || field >= ICAR_N_FIELDS || icar_hip_field_elem_size(field) != 4) { icar_set_error("box: REAL(4) fields only"); return 1; }
-    const int nx = c->d.nx, nz = c->d.nz, ny = c->d.ny;
-    if (icar_field_count(c, field) < (size_t)nx * nz * ny) { icar_set_error("box: 3-D fields only"); return 1; }
-    const int X = (field == ICAR_F_U || field == ICAR_F_JACOBIAN_U || field == ICAR_F_DZDX || field == ICAR_F_ZR_U) ? nx + 1 : nx;
-    const int Y = (field == ICAR_F_V || field == ICAR_F_JACOBIAN_V || field == ICAR_F_DZDY || field == ICAR_F_ZR_V) ? ny + 1 : ny;
-    if (i0 < 0 || ni < 1 || i0 + ni > X || j0 < 0 || nj < 1 || j0 + nj > Y) { icar_set_error("box: range outside the field"); return 1; }
-    float *f = which ? c->dqdt[field] : icar_field_f(c, field);
-    if (!f) { if (which) icar_set_error("box: dqdt_3d of this field is not on the device"); return 1; }
-    ScopedTimer t(c, "halo");
-    const dim3 g((ni + 63) / 64, nz, nj), b(64);
-    if (unpack) hipLaunchKernelGGL(k_box<true>, g, b, 0, c->stream, X, nz, i0, ni, j0, nj, f, buf);
-    else        hipLaunchKernelGGL(k_box<false>, g, b, 0, c->stream, X, nz, i0, ni, j0, nj, f, buf);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = blockIdx.y;
+    if (i >= d.nx) return;
+    float wprev = 0.0f, jwprev = 0.0f;
+    for (int k = 0; k < d.nz; ++k) {
+        const int c = d.idx(i, k, j);
+        const int cu = i + (d.nx + 1) * (k + d.nz * j);
+        const float du = u[cu + 1] * ju[cu + 1] - u[cu] * ju[cu];       // calc_divergence :207-210
+        const float dv = v[c + d.sj] * jv[c + d.sj] - v[c] * jv[c];
+        const float div = (du + dv) / dx;
+        float wk;
+        if (k == 0) wk = 0 - div * dz[c] / jw[c];                       // :141
+        else        wk = (wprev * jwprev - div * dz[c]) / jw[c];        // :143
+        w[c] = wk; wprev = wk; jwprev = jw[c];
+    }
+}
+
+int icar_balance_uvw_run(icar_hip_ctx *c, float dx, int update)
+{
+    // update != 0: wind.f90:341-360 balances the forcing tendencies u/v/w%meta_data%dqdt_3d instead of the winds
+    const float *u = update ? c->dqdt[ICAR_F_U] : icar_field_f(c, ICAR_F_U), *v = update ? c->dqdt[ICAR_F_V] : icar_field_f(c, ICAR_F_V);
+    const float *ju = icar_field_f(c, ICAR_F_JACOBIAN_U), *jv = icar_field_f(c, ICAR_F_JACOBIAN_V);
+    const float *jw = icar_field_f(c, ICAR_F_JACOBIAN_W), *dz = icar_field_f(c, ICAR_F_ADVECTION_DZ);
+    float *w = nullptr;
+    if (update) {
+        if (!c->dqdt[ICAR_F_W]) {
+            if (icar_hip_check(hipMalloc(&c->dqdt[ICAR_F_W], c->n3 * sizeof(float)), "hipMalloc(dqdt w)")) return 1;
+        }
+        w = c->dqdt[ICAR_F_W];
+        if (!u || !v) { icar_set_error("balance_uvw(update): upload the u and v dqdt_3d first (icar_hip_dqdt_upload)"); return 1; }
+    } else w = icar_field_f(c, ICAR_F_W, false);
+    if (!u || !v || !ju || !jv || !jw || !dz || !w) return 1;
+    dim3 g((c->d.nx + 63) / 64, c->d.ny), b(64);
+    hipLaunchKernelGGL(k_balance_uvw, g, b, 0, c->stream, c->d, u, v, w, ju, jv, jw, dz, dx);
     HIPCHK(hipGetLastError());
+    if (!update) icar_winds_changed(c);                          // w changed: the Courant winds are stale
     return 0;
 }

@@ -415,7 +415,7 @@ extern "C" {
 // forcing step's winds); update < 0 = as the reference decides it (first call of this context or not, wind.f90:297).
 int icar_hip_update_winds(icar_hip_ctx *c, int windtype, int wind_iterations, float dx, int halo, int update)
 {
-    if (!c) { icar_set_error("update_winds: null ctx"); return 1; }
+    if (!c) { icar_set_error("update_winds: null argument"); return 1; }
     if (wind_iterations < 0 || halo < 1) { icar_set_error("update_winds: wind_iterations >= 0, halo >= 1"); return 1; }
     HIPCHK(hipSetDevice(c->device));
     const int upd = update < 0 ? (c->step.winds_first ? 0 : 1) : (update ? 1 : 0);
@@ -444,9 +444,9 @@ int icar_hip_step_configure(icar_hip_ctx *c, const icar_hip_step_config *cfg, co
     return 0;
 }
 
-int icar_hip_model_time_set(icar_hip_ctx *c, double seconds) { if (!c) { icar_set_error("null ctx"); return 1; } c->step.model_time = seconds; c->step.failed = false; return 0; }
+int icar_hip_model_time_set(icar_hip_ctx *c, double seconds) { if (!c) { icar_set_error("model_time_set: null argument"); return 1; } c->step.model_time = seconds; c->step.failed = false; return 0; }
 double icar_hip_model_time(const icar_hip_ctx *c) { return c ? c->step.model_time : 0.0; }
-int icar_hip_mp_reset(icar_hip_ctx *c) { if (!c) { icar_set_error("null ctx"); return 1; } c->step.mp_last_model_time = -999.0; return 0; }
+int icar_hip_mp_reset(icar_hip_ctx *c) { if (!c) { icar_set_error("mp_reset: null argument"); return 1; } c->step.mp_last_model_time = -999.0; return 0; }
 
 int icar_hip_pbl_configure(icar_hip_ctx *c, int boundarylayer)
 {
@@ -460,7 +460,7 @@ int icar_hip_pbl_configure(icar_hip_ctx *c, int boundarylayer)
 
 int icar_hip_pbl(icar_hip_ctx *c, float dt)
 {
-    if (!c) { icar_set_error("null ctx"); return 1; }
+    if (!c) { icar_set_error("pbl: null argument"); return 1; }
     if (!cfg_ok(c, "pbl")) return 1;
     HIPCHK(hipSetDevice(c->device));
     return icar_pbl_run(c, dt);
@@ -468,7 +468,7 @@ int icar_hip_pbl(icar_hip_ctx *c, float dt)
 
 int icar_hip_mp(icar_hip_ctx *c, double dt, int halo, int subset)
 {
-    if (!c) { icar_set_error("null ctx"); return 1; }
+    if (!c) { icar_set_error("mp: null argument"); return 1; }
     if (!cfg_ok(c, "mp")) return 1;
     HIPCHK(hipSetDevice(c->device));
     return icar_mp_run(c, dt, halo, subset);
@@ -476,7 +476,7 @@ int icar_hip_mp(icar_hip_ctx *c, double dt, int halo, int subset)
 
 int icar_hip_advect_step(icar_hip_ctx *c, double dt)
 {
-    if (!c) { icar_set_error("null ctx"); return 1; }
+    if (!c) { icar_set_error("advect_step: null argument"); return 1; }
     if (!cfg_ok(c, "advect_step")) return 1;
     HIPCHK(hipSetDevice(c->device));
     return icar_step_advect(c, (float)dt);
@@ -506,7 +506,7 @@ int icar_hip_update_dt(icar_hip_ctx *c, double *dt_seconds)
 
 int icar_hip_substep(icar_hip_ctx *c, double dt_seconds, int enforce_limits)
 {
-    if (!c) { icar_set_error("null ctx"); return 1; }
+    if (!c) { icar_set_error("substep: null argument"); return 1; }
     if (!cfg_ok(c, "substep")) return 1;
     if (c->on_aux) { icar_set_error("substep: called between aux_begin and aux_end"); return 1; }
     HIPCHK(hipSetDevice(c->device));
@@ -517,7 +517,7 @@ int icar_hip_substep(icar_hip_ctx *c, double dt_seconds, int enforce_limits)
 // update_dt -> substep -> clock += dt, nothing of the host in between.  dt_last receives the last step's dt.
 int icar_hip_step_n(icar_hip_ctx *c, int nsteps, double *dt_last)
 {
-    if (!c) { icar_set_error("null ctx"); return 1; }
+    if (!c) { icar_set_error("step_n: null argument"); return 1; }
     if (!cfg_ok(c, "step_n")) return 1;
     if (c->on_aux) { icar_set_error("step_n: called between aux_begin and aux_end"); return 1; }
     HIPCHK(hipSetDevice(c->device));
@@ -534,7 +534,7 @@ int icar_hip_step_n(icar_hip_ctx *c, int nsteps, double *dt_last)
 
 int icar_hip_step(icar_hip_ctx *c, double end_time_seconds, int *nsteps)
 {
-    if (!c) { icar_set_error("null ctx"); return 1; }
+    if (!c) { icar_set_error("step: null argument"); return 1; }
     if (!cfg_ok(c, "step")) return 1;
     if (c->on_aux) { icar_set_error("step: called between aux_begin and aux_end"); return 1; }
     HIPCHK(hipSetDevice(c->device));

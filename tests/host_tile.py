@@ -1,5 +1,5 @@
 """Host-array double of the tile interface icar_amd.halo.HaloComm drives (TEST ONLY).
-Same face definitions / buffer layouts as the HIP pack kernels (icar_amd/csrc/capi.hip), written
+Same face definitions / buffer layouts as the HIP pack kernels (icar_amd/csrc/halo_pack.hip), written
 independently from exchangeable_obj.f90:248-356, so the GPU test can compare the two."""
 import numpy as np
 import torch

@@ -3,6 +3,8 @@ exchange emulated inside one process (two contexts on cuda:0, device buffers han
 import numpy as np
 import pytest
 import torch
+from icar_amd import _fields as F
+from icar_amd.capi import IcarHipError
 from icar_amd.grid import grid_t
 from host_tile import HostTile
 
@@ -17,29 +19,99 @@ def mk_domain(g, fields):
     return d
 
 
-@pytest.mark.parametrize("halo", [1, 2])
-def test_pack_unpack_match_host_double(halo):
-    nimg = 4
-    g = grid_t().set_grid_dimensions(70, 50, 7, nimg, 1, halo_width=halo)
-    ny, nz, nx = g.jme - g.jms + 1, 7, g.ime - g.ims + 1
-    rng = np.random.default_rng(5)
-    host = {0: rng.standard_normal((ny, nz, nx)).astype(np.float32), 4: rng.standard_normal((ny, nz, nx)).astype(np.float32),
-            7: rng.standard_normal((ny, nz, nx)).astype(np.float32)}
-    d = mk_domain(g, {"water_vapor": host[0], "potential_temperature": host[4], "cloud_ice_number": host[7]})
+ADVECTABLE = {fid: name for name, fid in F.NAMES.items() if fid < F.N_ADVECTABLE}      # ids 0..10
+
+
+def mk_scalars(g, ids, seed):
+    """a domain with random REAL(4) data in the advectable scalars `ids`, and the same arrays on the host"""
+    ny, nz, nx = g.jme - g.jms + 1, g.kme - g.kms + 1, g.ime - g.ims + 1
+    rng = np.random.default_rng(seed)
+    host = {fid: rng.standard_normal((ny, nz, nx)).astype(np.float32) for fid in ids}
+    return mk_domain(g, {ADVECTABLE[fid]: a for fid, a in host.items()}), host, rng
+
+
+# (nx, ny, nz, images, advectable ids): the tile of image 1 in memory is 36 x 26 x 7 (halo 1) / 37 x 27 x 7 (halo 2), 3 x 3 x 2 (the
+# smallest tile a context accepts: halo 2 does not fit) and 43 x 5 x 3 (halo 2: an N / S slab of nx nz halo = 258 elements, one
+# 256-thread block plus two threads); the small tiles carry all 11 advectable scalars, the largest blockIdx.y
+TILES = [(70, 50, 7, 4, [0, 4, 7]), (3, 3, 2, 1, list(range(11))), (43, 5, 3, 1, list(range(11)))]
+# (the first tile keeps the ids "1" and "2" it had as the only one)
+CASES = [pytest.param(t, h, id=str(h) if t is TILES[0] else f"{t[0]}x{t[1]}x{t[2]}-{h}") for t in TILES for h in (1, 2)]
+
+
+@pytest.mark.parametrize("tile, halo", CASES)
+def test_pack_unpack_match_host_double(tile, halo):
+    """every direction alone through icar_hip_halo_pack / _unpack against the host double; the fields are compared after EVERY
+    unpack, so a lone N / S unpack has to have written its whole rows, corners included, before E / W overwrite them"""
+    nxg, nyg, nz, nimg, ids = tile
+    g = grid_t().set_grid_dimensions(nxg, nyg, nz, nimg, 1, halo_width=halo)
+    d, host, rng = mk_scalars(g, ids, 5)
+    ny, nx = g.jme - g.jms + 1, g.ime - g.ims + 1
+    if nimg == 1:
+        assert (nx, ny) == (nxg, nyg)
+    if 2 * halo > min(nx, ny):                                   # refused, and nothing is written
+        for direction in range(4):
+            gb = d.new_buffer(d.halo_count(direction, halo) * len(ids))
+            for call in (d.halo_pack, d.halo_unpack):
+                with pytest.raises(IcarHipError, match="halo width"):
+                    call(direction, halo, ids, gb)
+        for fid in ids:
+            assert np.array_equal(d.get(ADVECTABLE[fid]), host[fid]), fid
+        d.close()
+        return
     ht = HostTile(g, {k: v.copy() for k, v in host.items()})
-    ids = [0, 4, 7]
     for direction in range(4):
         n = d.halo_count(direction, halo)
         assert n == ht.halo_count(direction, halo)
-        gb = d.new_buffer(n * 3); hb = ht.new_buffer(n * 3)
+        gb = d.new_buffer(n * len(ids)); hb = ht.new_buffer(n * len(ids))
         d.halo_pack(direction, halo, ids, gb); d.synchronize()
         ht.halo_pack(direction, halo, ids, hb)
         assert torch.equal(gb.cpu(), hb), f"pack dir {direction}"
-        inbox = torch.from_numpy(rng.standard_normal(n * 3).astype(np.float32))
+        inbox = torch.from_numpy(rng.standard_normal(n * len(ids)).astype(np.float32))
         d.halo_unpack(direction, halo, ids, inbox.cuda()); d.synchronize()
         ht.halo_unpack(direction, halo, ids, inbox)
-    for fid, name in ((0, "water_vapor"), (4, "potential_temperature"), (7, "cloud_ice_number")):
-        assert np.array_equal(d.get(name), ht.f[fid]), name
+        for fid in ids:
+            assert np.array_equal(d.get(ADVECTABLE[fid]), ht.f[fid]), f"field {fid} after the unpack of dir {direction}"
+    assert all(not np.array_equal(ht.f[fid], host[fid]) for fid in ids)
+    d.close()
+
+
+def test_halo_pack_refusals():
+    """the argument checks of the one packer, through all four entry points, on the smallest tile (3 x 3 x 2): a bad direction,
+    a halo width that does not fit, a field that is no exchangeable scalar and more fields than a launch takes all return
+    non-zero with a text and leave the fields (and the buffers) as they were; no fields is no work and no error"""
+    import ctypes
+    from icar_amd.capi import lib
+    g = grid_t().set_grid_dimensions(3, 3, 2, 1, 1, halo_width=1)
+    ids = list(range(11))
+    d, host, _ = mk_scalars(g, ids, 3)
+    L = lib()
+    nbuf = 13 * 3 * 2 * 2                                        # 13 fields of the largest face (halo 2)
+    buf = torch.full((nbuf,), 7.0, dtype=torch.float32, device="cuda:0")
+    ptr = ctypes.c_void_p(buf.data_ptr()); ptrs = (ctypes.c_void_p * 1)(ptr)
+    arr = lambda v: (ctypes.c_int * len(v))(*v)
+    entries = [lambda x, h, f, n: L.icar_hip_halo_pack(d.ctx, x, h, arr(f), n, ptr),
+               lambda x, h, f, n: L.icar_hip_halo_unpack(d.ctx, x, h, arr(f), n, ptr),
+               lambda x, h, f, n: L.icar_hip_halo_pack_dirs(d.ctx, 1, arr([x]), h, arr(f), n, ptrs),
+               lambda x, h, f, n: L.icar_hip_halo_unpack_dirs(d.ctx, 1, arr([x]), h, arr(f), n, ptrs)]
+
+    def untouched(what):
+        d.synchronize()
+        for fid in ids:
+            assert d.get(ADVECTABLE[fid]).tobytes() == host[fid].tobytes(), (what, fid)
+        assert bool((buf == 7.0).all()), what
+
+    # what is refused: (direction, halo, fields, nfields) and the words of the text that say which check refused it
+    bad = {"dir -1": (-1, 1, [0], 1, b"dir must be 0..3"), "dir 4": (4, 1, [0], 1, b"dir must be 0..3"),
+           "halo 0": (0, 0, [0], 1, b"bad halo width"), "halo 2": (0, 2, [0], 1, b"bad halo width"),
+           "field id 11": (0, 1, [11], 1, b"only exchangeable scalars"), "13 fields": (0, 1, ids + [0, 1], 13, b"too many fields")}
+    for what, (*args, words) in bad.items():
+        for k, call in enumerate(entries):
+            assert call(*args) != 0, (what, k)
+            assert words in L.icar_hip_last_error(), (what, k, L.icar_hip_last_error())
+            untouched((what, k))
+    for k, call in enumerate(entries):
+        assert call(0, 1, [0], 0) == 0, k
+        untouched(("nfields = 0", k))
     d.close()
 
 

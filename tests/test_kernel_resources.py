@@ -39,5 +39,5 @@ def test_thompson_pack_resources():
 
 def test_side_stream_kernels_fit_beside_the_advection():
     """what runs on the second stream while k_mpdata_fused holds 2 x 248 of a SIMD's 512 registers must fit into the rest"""
-    r = B.kernel_resources("capi.hip")["k_max_courant"]
+    r = B.kernel_resources("cfl.hip")["k_max_courant"]
     assert r["VGPRs"] <= 16 and r["ScratchSize [bytes/lane]"] == 0, r
