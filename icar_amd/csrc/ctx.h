@@ -39,6 +39,7 @@ struct IcarStepState {
     int winds_scheme = 0, winds_dens = 0; float winds_dt = 0.f;   // what the Courant winds on the device were set up for
     float *h_val = nullptr;                  // pinned: the reduced CFL maximum
     bool early_open = false, early_wreal = false, early_face = false;   // a sub-step whose dt-independent opening is already in flight
+    bool early_lazy = false;                 // ... and that opening wrote only the diagnostics the device reads (not a call's last sub-step)
     bool failed = false;                 // a sub-step was abandoned half-applied (timestep.hip: update_dt_opened): the fields are not a model state any more
     bool winds_first = true;                 // wind.f90:297 `.not. allocated(domain%sintheta)`: update_winds has not run yet
     int boundarylayer = 0;                   // options%physics%boundarylayer (icar_hip_pbl_configure): 0, 1 or ICAR_PBL_SIMPLE
@@ -138,7 +139,7 @@ int icar_pbl_nsubsteps_copy(icar_hip_ctx *c, int *out, int n);
 // timestep.hip
 int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset);      // halo / subset < 0: argument not present
 int icar_update_dt(icar_hip_ctx *c, double *seconds);
-int icar_substep(icar_hip_ctx *c, double dt, bool enforce);
+int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last = true);
 // halo_pack.hip
 int icar_halo_pack_dirs(icar_hip_ctx *c, int ndir, const int *dirs, int halo, const int *fields, int n, void *const *bufs, bool unpack);
 int icar_box_copy(icar_hip_ctx *c, int field, int which, int i0, int ni, int j0, int nj, float *buf, bool unpack);
@@ -155,8 +156,9 @@ int icar_mass_conservative_acceleration(icar_hip_ctx *c, int update);
 int icar_iterative_winds_sweep(icar_hip_ctx *c, float dx, int nsweeps, int update);
 int icar_make_winds_grid_relative(icar_hip_ctx *c, int update);
 // step.hip
-enum { ICAR_DIAG_CELL = 4, ICAR_DIAG_FACE = 8 };     // finer parts of icar_diagnostic_update_run, internal
+enum { ICAR_DIAG_CELL = 4, ICAR_DIAG_FACE = 8, ICAR_DIAG_EXNER = 16, ICAR_DIAG_EXNER_RHO = 32 };     // finer parts of icar_diagnostic_update_run, internal
 int icar_diagnostic_update_run(icar_hip_ctx *c, int parts);
+bool icar_diag_columns_on(const icar_hip_ctx *c);      // column integrals (ivt, iwv, iwl, iwi) are computed on the device
 int icar_apply_forcing_run(icar_hip_ctx *c, double dt, const int *fields, const int *fb, int n, int w, int e, int s, int nn);
 int icar_enforce_limits_run(icar_hip_ctx *c, const int *fields, int n);
 // mp_thompson.hip, thompson_tables.hip

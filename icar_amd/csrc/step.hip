@@ -21,23 +21,39 @@ __device__ __forceinline__ float exner_function(float pressure)
 //                T just written, u, v -- nothing the microphysics touches, so the sub-step issues it on the second stream beside
 //                the interior launch (timestep.hip).
 // T(k+-1) read back from memory is the same th * exner the cell kernel stored, so the split changes no result.
+// ST / SR: store temperature / density.  Inside icar_hip_step / _step_n a sub-step that is not the call's last one stores only
+// what something on the device reads before the next diagnostic_update (timestep.hip): exner always, density for the schemes
+// that read it; the values themselves are the same expressions either way.
+template <bool ST, bool SR>
 __global__ void __launch_bounds__(256)
 k_diag_cell(size_t n4, size_t n, const float *__restrict__ p, const float *__restrict__ th, float *__restrict__ exner,
             float *__restrict__ T, float *__restrict__ rho)
 {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < n4) {
-        const float4 pc = ((const float4 *)p)[t], tc = ((const float4 *)th)[t];
+        const float4 pc = ((const float4 *)p)[t];
         float4 ex, tt, rr;
         ex.x = exner_function(pc.x); ex.y = exner_function(pc.y); ex.z = exner_function(pc.z); ex.w = exner_function(pc.w);
-        tt.x = tc.x * ex.x; tt.y = tc.y * ex.y; tt.z = tc.z * ex.z; tt.w = tc.w * ex.w;                     // :95
-        rr.x = pc.x / (Rd * tt.x); rr.y = pc.y / (Rd * tt.y); rr.z = pc.z / (Rd * tt.z); rr.w = pc.w / (Rd * tt.w);   // :101
-        ((float4 *)exner)[t] = ex; ((float4 *)T)[t] = tt; ((float4 *)rho)[t] = rr;
+        ((float4 *)exner)[t] = ex;
+        if (ST || SR) {
+            const float4 tc = ((const float4 *)th)[t];
+            tt.x = tc.x * ex.x; tt.y = tc.y * ex.y; tt.z = tc.z * ex.z; tt.w = tc.w * ex.w;                     // :95
+            if (ST) ((float4 *)T)[t] = tt;
+        }
+        if (SR) {
+            rr.x = pc.x / (Rd * tt.x); rr.y = pc.y / (Rd * tt.y); rr.z = pc.z / (Rd * tt.z); rr.w = pc.w / (Rd * tt.w);   // :101
+            ((float4 *)rho)[t] = rr;
+        }
     } else {
         const size_t c = 4 * n4 + (t - n4);                       // the cells left over when n is not a multiple of 4
         if (c < n) {
-            const float pc = p[c], ex = exner_function(pc), tt = th[c] * ex;
-            exner[c] = ex; T[c] = tt; rho[c] = pc / (Rd * tt);
+            const float pc = p[c], ex = exner_function(pc);
+            exner[c] = ex;
+            if (ST || SR) {
+                const float tt = th[c] * ex;
+                if (ST) T[c] = tt;
+                if (SR) rho[c] = pc / (Rd * tt);
+            }
         }
     }
 }
@@ -191,10 +207,32 @@ k_enforce_limits(size_t n, LimitArgs a)
 // The sub-step splits 1 further: ICAR_DIAG_CELL (exner, T, density + the column integrals when they are on the device) before
 // the microphysics, ICAR_DIAG_FACE (interface values, mass-point winds) beside it; 1 = both.  With column integrals on the
 // device (they read the face kernel's outputs AND the water species) everything runs at ICAR_DIAG_CELL and _FACE is empty.
+// ICAR_DIAG_EXNER / ICAR_DIAG_EXNER_RHO: the cell kernel storing exner only / exner and density, for a sub-step whose other
+// diagnostics nothing can observe (timestep.hip decides; with column integrals on the device they are the full ICAR_DIAG_CELL).
+bool icar_diag_columns_on(const icar_hip_ctx *c)
+{
+    return c->field[ICAR_F_IVT] || c->field[ICAR_F_IWV] || c->field[ICAR_F_IWL] || c->field[ICAR_F_IWI];
+}
+
 int icar_diagnostic_update_run(icar_hip_ctx *c, int parts)
 {
     const float *u = (const float *)c->field[ICAR_F_U], *v = (const float *)c->field[ICAR_F_V];
     if (parts & 1) parts |= ICAR_DIAG_CELL | ICAR_DIAG_FACE;
+    if ((parts & (ICAR_DIAG_EXNER | ICAR_DIAG_EXNER_RHO)) && ((parts & ICAR_DIAG_CELL) || icar_diag_columns_on(c)))
+        parts = (parts & ~(ICAR_DIAG_EXNER | ICAR_DIAG_EXNER_RHO)) | ICAR_DIAG_CELL;
+    if (parts & (ICAR_DIAG_EXNER | ICAR_DIAG_EXNER_RHO)) {
+        const float *p = icar_field_f(c, ICAR_F_PRESSURE), *th = icar_field_f(c, ICAR_F_POTENTIAL_TEMPERATURE);
+        float *ex = icar_field_f(c, ICAR_F_EXNER, false), *rho = icar_field_f(c, ICAR_F_DENSITY, false);
+        if (!p || !th || !ex || !rho) return 1;
+        ScopedTimer t(c, "diag");
+        const size_t n4 = c->n3 / 4, rest = c->n3 - 4 * n4, nthr = n4 + rest;
+        const dim3 g((unsigned)((nthr + 255) / 256)), b(256);
+        if (parts & ICAR_DIAG_EXNER_RHO) {
+            c->winds_valid = false;                              // density is rewritten, as below
+            hipLaunchKernelGGL((k_diag_cell<false, true>), g, b, 0, c->stream, n4, c->n3, p, th, ex, (float *)nullptr, rho);
+        } else
+            hipLaunchKernelGGL((k_diag_cell<false, false>), g, b, 0, c->stream, n4, c->n3, p, th, ex, (float *)nullptr, (float *)nullptr);
+    }
     if (parts & (ICAR_DIAG_CELL | ICAR_DIAG_FACE)) {
     const float *p = icar_field_f(c, ICAR_F_PRESSURE), *th = icar_field_f(c, ICAR_F_POTENTIAL_TEMPERATURE);
     if (!p || !th) return 1;
@@ -212,7 +250,7 @@ int icar_diagnostic_update_run(icar_hip_ctx *c, int parts)
         c->winds_valid = false;                                  // density is rewritten: Courant winds (advect_density) are stale -- u, v, w are
                                                                  // not: a prefetched CFL maximum of them stays valid (wind_version untouched)
         const size_t n4 = c->n3 / 4, rest = c->n3 - 4 * n4, nthr = n4 + rest;
-        hipLaunchKernelGGL(k_diag_cell, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, c->stream, n4, c->n3, p, th, ex, T, rho);
+        hipLaunchKernelGGL((k_diag_cell<true, true>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, c->stream, n4, c->n3, p, th, ex, T, rho);
     }
     if (columns ? (parts & ICAR_DIAG_CELL) : (parts & ICAR_DIAG_FACE)) {          // (with column integrals: at the CELL call)
         dim3 g((c->d.nx + 63) / 64, (c->d.nz + 3) / 4, c->d.ny), b(64, 4);

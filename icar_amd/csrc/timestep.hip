@@ -9,11 +9,16 @@
 //   diagnostic_update part 1 (exner, T, rho, ...)
 //   [pbl, when icar_hip_pbl_configure switched it on: it reads u_mass / v_mass, so the whole of part 1 runs in front of it]
 //   mp(subset=1) interior                                 mp(halo=1) strips -> halo_send (pack + RCCL)   time_step.f90:512-526
-//   |                                                     setup_module_winds (+ MPDATA coefficients) of the advect() that follows
+//   |                                                     interface values, mass-point winds (k_diag_face)
+//   |                                                     setup_module_winds (+ MPDATA coefficients) of the advect() that follows,
+//   |                                                     w_real from the same launch
 //   halo_retrieve (unpack)  <----------------------------- join
-//   advect                                                w_real diagnostic, forcing of u, v, w, p, CFL reduction of the next step
+//   advect                                                forcing of u, v, w, p, CFL reduction of the next step
 //   forcing of the advected scalars (boundary ring) <----- join
 //   enforce_limits (last two sub-steps)
+// Inside icar_hip_step / _step_n a sub-step that is not the call's last one leaves out the diagnostics nobody can observe
+// (lazy_diag_part below): with Thompson only exner is written, with mp_simple / WSM6 exner and density; k_diag_face and w_real run
+// in the call's last sub-step only.  Every single-sub-step entry point is its own last sub-step.
 #include "ctx.h"
 #include <chrono>
 #include "comm.h"
@@ -201,16 +206,40 @@ bool icar_substep_can_open_early(icar_hip_ctx *c)
         && g.prefetch_dt && (g.cfl_strictness == 3 || g.cfl_strictness == 4) && icar_cfl_prefetch_waiting(c) && !c->on_aux;
 }
 
-static int substep_open(icar_hip_ctx *c, double dt, bool dt_known, bool &wreal_later, bool &face_later)
+// ---- diagnostics where they can be observed -------------------------------------------------------------------------------
+// icar_hip_step / _step_n run many sub-steps inside one library call, and the host cannot look between them: temperature,
+// density, the interface values, the mass-point winds and w_real of a sub-step that is not the call's last are seen by nobody
+// unless something on the device reads them before the next diagnostic_update rewrites them.  Who reads what:
+//   exner                 every microphysics scheme                                   -> always written
+//   density               mp_simple, WSM6, WSM3, pbl_simple, the Courant winds with advect_density
+//   temperature           the interface kernel only (k_diag_face)
+//   u_mass, v_mass, interface values   pbl_simple, the column integrals
+//   w_real                WSM3
+// Returns what the cell kernel of such a sub-step stores (ICAR_DIAG_EXNER / ICAR_DIAG_EXNER_RHO; its face kernel and w_real are
+// then left out), or 0: everything, as a single sub-step does.  When in doubt, everything.
+static int lazy_diag_part(icar_hip_ctx *c, bool last)
+{
+    const icar_hip_step_config &g = c->step.cfg;
+    if (last || !g.diagnostics) return 0;
+    if (c->step.boundarylayer == ICAR_PBL_SIMPLE || g.advect_density || icar_diag_columns_on(c)) return 0;
+    if (g.microphysics == kMP_THOMPSON) return ICAR_DIAG_EXNER;                                   // reads exner, p, th, dz
+    if (g.microphysics == kMP_SB04 || g.microphysics == kMP_WSM6) return ICAR_DIAG_EXNER_RHO;     // ... and density
+    return 0;                                                                                     // WSM3 (w_real, density), no microphysics
+}
+
+static int substep_open(icar_hip_ctx *c, double dt, bool dt_known, bool &wreal_later, bool &face_later, int lazy)
 {
     const icar_hip_step_config &g = c->step.cfg;
     const bool adv = (g.advection == ICAR_ADV_UPWIND || g.advection == ICAR_ADV_MPDATA);
     wreal_later = false; face_later = false;
     if (g.diagnostics) {
         if (g.microphysics != kMP_WSM3) {
-            face_later = true;
-            if (icar_diagnostic_update_run(c, ICAR_DIAG_CELL)) return 1;
-            wreal_later = true;
+            if (lazy) { if (icar_diagnostic_update_run(c, lazy)) return 1; }
+            else {
+                face_later = true;
+                if (icar_diagnostic_update_run(c, ICAR_DIAG_CELL)) return 1;
+                wreal_later = true;
+            }
         } else if (icar_diagnostic_update_run(c, 3)) return 1;
     }
     if (icar_hip_aux_fork(c)) return 1;
@@ -231,11 +260,13 @@ static int substep_open(icar_hip_ctx *c, double dt, bool dt_known, bool &wreal_l
     return 0;
 }
 
-int icar_substep_open_early(icar_hip_ctx *c)
+// maybe_last: the sub-step may turn out to be the call's last one -- it then opens with every diagnostic
+static int substep_open_early(icar_hip_ctx *c, bool maybe_last)
 {
     bool wl, fl;
-    if (substep_open(c, 0.0, false, wl, fl)) return 1;
-    c->step.early_open = true; c->step.early_wreal = wl; c->step.early_face = fl;
+    const int lazy = lazy_diag_part(c, maybe_last);
+    if (substep_open(c, 0.0, false, wl, fl, lazy)) return 1;
+    c->step.early_open = true; c->step.early_wreal = wl; c->step.early_face = fl; c->step.early_lazy = lazy != 0;
     return 0;
 }
 
@@ -256,7 +287,8 @@ static int update_dt_opened(icar_hip_ctx *c, double *dt)
     return 1;
 }
 
-int icar_substep(icar_hip_ctx *c, double dt, bool enforce)
+// last: the sub-step's diagnostics are what the caller sees (every single-sub-step entry point; the last pass of the loops)
+int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
 {
     const icar_hip_step_config &g = c->step.cfg;
     const float dtf = (float)dt;
@@ -266,10 +298,12 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce)
     bool wreal_later = false, face_later = false, wreal_done = false;
     const bool early = c->step.early_open;
     c->step.early_open = false;
+    const int lazy = stepping ? lazy_diag_part(c, last) : 0;              // (dt <= 1e-3: diagnostic_update is all the pass does)
     if (early) {
-        // the opening is in flight (icar_substep_open_early); what it left out: the wind setup of the advect() below, on the second stream
+        // the opening is in flight (substep_open_early); what it left out: the wind setup of the advect() below, on the second stream
         wreal_later = c->step.early_wreal; face_later = c->step.early_face;
         if (!stepping) { icar_set_error("substep: opened early but dt <= 1e-3"); return 1; }
+        if (last && c->step.early_lazy) { icar_set_error("substep: the call's last sub-step was opened without its diagnostics"); return 1; }
         if (adv) {
             AuxScope aux(c);
             if (aux.begin()) return 1;
@@ -279,12 +313,17 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce)
     } else
     if (g.diagnostics) {                                                          // :474
         if (g.microphysics != kMP_WSM3) {                                         // WSM3 reads w_real
+            if (lazy) {
+                // not the call's last sub-step: only what the device reads before the next diagnostic_update (lazy_diag_part)
+                if (icar_diagnostic_update_run(c, lazy)) return 1;
+            } else {
             // exner / T / density now; the interface values and mass-point winds (nothing the microphysics reads or writes)
             // beside the interior launch below
             face_later = stepping && g.microphysics != 0 && !pbl;                 // (simple_pbl reads u_mass and v_mass: nothing of part 1 can wait)
             if (icar_diagnostic_update_run(c, face_later ? ICAR_DIAG_CELL : 1)) return 1;
             if (stepping) wreal_later = true;                                     // beside the advection, below
             else if (icar_diagnostic_update_run(c, 2)) return 1;
+            }
         } else if (icar_diagnostic_update_run(c, 3)) return 1;
     }
     if (!stepping) return 0;
@@ -510,7 +549,7 @@ int icar_hip_substep(icar_hip_ctx *c, double dt_seconds, int enforce_limits)
     if (!cfg_ok(c, "substep")) return 1;
     if (c->on_aux) { icar_set_error("substep: called between aux_begin and aux_end"); return 1; }
     HIPCHK(hipSetDevice(c->device));
-    return icar_substep(c, dt_seconds, enforce_limits != 0);
+    return icar_substep(c, dt_seconds, enforce_limits != 0, true);
 }
 
 // nsteps sub-steps of the loop without an end time (a benchmark's "K passes of the hot path", a host that counts steps):
@@ -523,9 +562,10 @@ int icar_hip_step_n(icar_hip_ctx *c, int nsteps, double *dt_last)
     HIPCHK(hipSetDevice(c->device));
     double dt = 0.0;
     for (int n = 0; n < nsteps; ++n) {
-        if (icar_substep_can_open_early(c) && icar_substep_open_early(c)) return 1;
+        const bool last = n == nsteps - 1;                                       // its diagnostics are the ones the caller sees
+        if (icar_substep_can_open_early(c) && substep_open_early(c, last)) return 1;
         if (update_dt_opened(c, &dt)) return 1;
-        if (icar_substep(c, dt, false)) return 1;
+        if (icar_substep(c, dt, false, last)) return 1;
         c->step.model_time += dt;
     }
     if (dt_last) *dt_last = dt;
@@ -541,11 +581,15 @@ int icar_hip_step(icar_hip_ctx *c, double end_time_seconds, int *nsteps)
     int n = 0;
     while (c->step.model_time < end_time_seconds) {                              // :462
         double dt;
-        // (update_dt caps dt at 120 s, :417: farther than that from the end no clamp can shorten this step)
-        if (end_time_seconds - c->step.model_time > 120.0 && icar_substep_can_open_early(c) && icar_substep_open_early(c)) return 1;
+        // (update_dt caps dt at 120 s, :417: farther than that from the end no clamp can shorten this step; farther than two
+        // caps from it the step cannot be the last one either, whatever the rounding of the clock)
+        const double left = end_time_seconds - c->step.model_time;
+        if (left > 120.0 && icar_substep_can_open_early(c) && substep_open_early(c, !(left > 240.0))) return 1;
         if (update_dt_opened(c, &dt)) return 1;                                  // :465
         if (c->step.model_time + dt > end_time_seconds) dt = end_time_seconds - c->step.model_time;       // :469-471
-        if (icar_substep(c, dt, (end_time_seconds - c->step.model_time) < dt * 2)) return 1;               // :474-539
+        // the last sub-step is the one after which the loop's own test (:462, on the clock of :547) fails
+        const bool last = !(c->step.model_time + dt < end_time_seconds);
+        if (icar_substep(c, dt, (end_time_seconds - c->step.model_time) < dt * 2, last)) return 1;          // :474-539
         c->step.model_time += dt;                                                // :547
         ++n;
     }

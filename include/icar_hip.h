@@ -428,7 +428,12 @@ int icar_hip_co_max(icar_hip_ctx *ctx, double *value);
  *                           An error from icar_hip_step / icar_hip_step_n leaves the fields undefined (the reference STOPs
  *                           where update_dt fails, :322-328): when the failing sub-step had already been opened the context
  *                           is marked failed and every stepping entry point returns an error until the caller has reloaded
- *                           the fields and set the clock again (icar_hip_model_time_set)
+ *                           the fields and set the clock again (icar_hip_model_time_set).
+ *                           The DIAGNOSTIC fields (temperature, density, pressure_interface, surface_pressure,
+ *                           temperature_interface, u_mass, v_mass, w_real) after icar_hip_step / icar_hip_step_n are those of
+ *                           the call's LAST sub-step -- what the reference leaves, too; the sub-steps before it write only the
+ *                           diagnostics that something on the device reads (exner always), since the host cannot look between
+ *                           them.  They are unspecified if the call fails part-way.  icar_hip_substep is its own last sub-step.
  * The library keeps the model clock (domain%model_time) and mp_driver.f90's SAVE variable last_model_time. */
 typedef struct icar_hip_step_config {
     int advection;                  /* options%physics%advection: 0, ICAR_ADV_UPWIND, ICAR_ADV_MPDATA            */
@@ -461,7 +466,8 @@ int icar_hip_advect_step(icar_hip_ctx *ctx, double dt);
 int icar_hip_substep(icar_hip_ctx *ctx, double dt_seconds, int enforce_limits);
 int icar_hip_step(icar_hip_ctx *ctx, double end_time_seconds, int *nsteps);
 /* the same loop for a given NUMBER of sub-steps (update_dt -> substep -> clock += dt each), no end-of-interval clamp and no
- * enforce_limits: what a benchmark times as "K passes of the hot path".  dt_last (may be NULL) receives the last dt. */
+ * enforce_limits: what a benchmark times as "K passes of the hot path".  dt_last (may be NULL) receives the last dt.
+ * As with icar_hip_step, the diagnostic fields are those of the call's last sub-step (unspecified if the call fails part-way). */
 int icar_hip_step_n(icar_hip_ctx *ctx, int nsteps, double *dt_last);
 
 /* ---- measurement helpers --------------------------------------------------------------------- */
