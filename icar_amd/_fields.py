@@ -11,7 +11,9 @@ IVT, IWV, IWL, IWI = 37, 38, 39, 40
 ZR_U, ZR_V = 41, 42
 SINTHETA, COSTHETA = 43, 44
 TERRAIN, LAND_MASK = 45, 46
-N_FIELDS = 47
+N_FIELDS = 47                   # ICAR_N_FIELDS: the ids above
+LATITUDE, LONGITUDE, SHORTWAVE, LONGWAVE, CLOUD_FRACTION = 47, 48, 49, 50, 51      # ra_simple's block behind them
+N_FIELD_IDS = 52                # ICAR_N_FIELD_IDS: every id is below this one
 
 NAMES = {
     "water_vapor": WATER_VAPOR, "cloud_water_mass": CLOUD_WATER, "rain_mass": RAIN, "snow_mass": SNOW,
@@ -24,6 +26,7 @@ NAMES = {
     "u_mass": U_MASS, "v_mass": V_MASS, "w_real": W_REAL, "dzdx": DZDX, "dzdy": DZDY, "surface_pressure": SURFACE_PRESSURE,
     "z": Z, "nsquared": NSQUARED, "ivt": IVT, "iwv": IWV, "iwl": IWL, "iwi": IWI, "zr_u": ZR_U, "zr_v": ZR_V, "sintheta": SINTHETA, "costheta": COSTHETA,
     "terrain": TERRAIN, "land_mask": LAND_MASK,
+    "latitude": LATITUDE, "longitude": LONGITUDE, "shortwave": SHORTWAVE, "longwave": LONGWAVE, "cloud_fraction": CLOUD_FRACTION,
     "accumulated_precipitation": PRECIPITATION, "accumulated_snowfall": SNOWFALL, "graupel": GRAUPEL_ACC,
 }
 IS_2DD = {PRECIPITATION, SNOWFALL, GRAUPEL_ACC, SINTHETA, COSTHETA}

@@ -31,6 +31,7 @@ SYMBOLS = [
     "icar_hip_linwinds_build_lut", "icar_hip_linwinds_build_lut_varying", "icar_hip_linwinds_lut_download", "icar_hip_linwinds_lut_upload", "icar_hip_linwinds_lut_entry",
     "icar_hip_linwinds_perturbation_download", "icar_hip_linwinds_perturbation_upload", "icar_hip_spatial_winds",
     "icar_hip_pbl_simple", "icar_hip_pbl_configure", "icar_hip_pbl", "icar_hip_pbl_nsubsteps",
+    "icar_hip_ra_simple", "icar_hip_rad_configure", "icar_hip_rad_calendar", "icar_hip_rad",
 ]
 
 
@@ -102,6 +103,10 @@ def lib():
         L.icar_hip_pbl_configure.argtypes = [vp, ci]
         L.icar_hip_pbl.argtypes = [vp, ctypes.c_float]
         L.icar_hip_pbl_nsubsteps.argtypes = [vp, vp, ci]
+        L.icar_hip_ra_simple.argtypes = [vp, ctypes.c_float, ci, ci, ci, ci, ci, ci, ci]
+        L.icar_hip_rad_configure.argtypes = [vp, ci]
+        L.icar_hip_rad_calendar.argtypes = [vp, ci, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+        L.icar_hip_rad.argtypes = [vp, ctypes.c_float]
         _lib = L
     return _lib
 

@@ -11,6 +11,9 @@ kMP_WSM3 = 6
 kPBL_BASIC = 1                  # icar_constants.f90:354-356
 kPBL_SIMPLE = 2
 kPBL_YSU = 3
+kRA_BASIC = 1                   # icar_constants.f90 (radiation)
+kRA_SIMPLE = 2
+kRA_RRTMG = 3
 kLC_LAND = 1                    # land_mask values, icar_constants.f90
 kLC_WATER = 2
 kDEFAULT_HALO_SIZE = 1          # icar_constants.f90:320

@@ -43,6 +43,11 @@ struct IcarStepState {
     bool failed = false;                 // a sub-step was abandoned half-applied (timestep.hip: update_dt_opened): the fields are not a model state any more
     bool winds_first = true;                 // wind.f90:297 `.not. allocated(domain%sintheta)`: update_winds has not run yet
     int boundarylayer = 0;                   // options%physics%boundarylayer (icar_hip_pbl_configure): 0, 1 or ICAR_PBL_SIMPLE
+    int radiation = 0;                       // options%physics%radiation (icar_hip_rad_configure): 0, 1 or ICAR_RA_SIMPLE
+    // icar_hip_rad_calendar: the calendar and, on the library's clock, 1 January 00:00 of the model time's year with the lengths of that year and the next
+    bool rad_calendar_set = false;
+    int rad_calendar = 0;
+    double rad_year_start = 0.0, rad_year_days = 365.0, rad_next_year_days = 365.0;
 };
 
 // component indices of the per-cell coefficients in icar_hip_ctx::mpc (k_mpdata_coef in mpdata.hip says what they hold): the first
@@ -65,8 +70,8 @@ struct icar_hip_ctx {
     hipStream_t aux = nullptr, main_saved = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool on_aux = false;
-    void *field[ICAR_N_FIELDS] = {nullptr};
-    float *dqdt[ICAR_N_FIELDS] = {nullptr};    // variable_t%dqdt_3d mirrors (apply_forcing)
+    void *field[ICAR_N_FIELD_IDS] = {nullptr};
+    float *dqdt[ICAR_N_FIELD_IDS] = {nullptr};    // variable_t%dqdt_3d mirrors (apply_forcing)
     // advection scratch (A1-A5)
     float *U = nullptr, *V = nullptr, *W = nullptr, *Wdz = nullptr;
     float *mpc = nullptr;                // MPDATA: the scalar-independent coefficients of this step's winds, mpc_bytes(n3) (MPC_* above)
@@ -88,6 +93,8 @@ struct icar_hip_ctx {
     float *wgr_tmp = nullptr;            // make_winds_grid_relative: rotated mass-grid u | v (2 x n3)
     float *pbl_kq = nullptr;             // pbl_simple.hip: Kq_m of the last call (n3), allocated on first use
     unsigned *pbl_rowmax = nullptr;      // pbl_simple.hip: bit pattern of maxval(Kq/dz) of every row (ny)
+    float *ra_coslat = nullptr;          // ra_simple.hip: cos_lat_m | sin_lat_m of ra_simple_init (2 x nx*ny), allocated on first use
+    bool ra_lat_valid = false;           // ... and whether they are those of the ICAR_F_LATITUDE on the device
     // reductions / flags
     float *d_red = nullptr;              // small device scratch for reductions
     std::vector<float> dzl_host;         // dz_levels last uploaded behind d_red (compute_dt re-sends them only when they change)
@@ -136,6 +143,10 @@ int icar_mp_simple_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int ti
 int icar_pbl_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);
 int icar_pbl_run(icar_hip_ctx *c, float dt);                                // pbl(domain, options, dt): the configured scheme on the step's tile
 int icar_pbl_nsubsteps_copy(icar_hip_ctx *c, int *out, int n);
+// ra_simple.hip
+int icar_ra_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte, int runlw, int calendar, double D, double year_days);
+int icar_rad_clock(icar_hip_ctx *c, double model_time, double *D, double *year_days);   // day of the year under icar_hip_rad_calendar's anchor
+int icar_rad_run(icar_hip_ctx *c, float dt);                                // rad(domain, options, dt): the configured scheme on the step's tile
 // timestep.hip
 int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset);      // halo / subset < 0: argument not present
 int icar_update_dt(icar_hip_ctx *c, double *seconds);

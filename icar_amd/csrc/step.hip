@@ -288,7 +288,7 @@ int icar_apply_forcing_run(icar_hip_ctx *c, double dt, const int *fields, const 
     ForceArgs a;
     for (int m = 0; m < n; ++m) {
         const int f = fields[m];
-        if (f < 0 || f >= ICAR_N_FIELDS || f == ICAR_F_PRECIPITATION || f == ICAR_F_SNOWFALL || f == ICAR_F_GRAUPEL_ACC || f == ICAR_F_SURFACE_PRESSURE || f == ICAR_F_TERRAIN || f == ICAR_F_LAND_MASK) {
+        if (f < 0 || f >= ICAR_N_FIELD_IDS || f == ICAR_F_PRECIPITATION || f == ICAR_F_SNOWFALL || f == ICAR_F_GRAUPEL_ACC || f == ICAR_F_SURFACE_PRESSURE || f >= ICAR_F_TERRAIN) {
             icar_set_error("apply_forcing: only 3-D REAL(4) fields"); return 1;
         }
         a.x[m] = icar_field_f(c, f);

@@ -7,6 +7,8 @@
 // What runs beside what (same launches, operands and results as the plain sequence):
 //   main stream (the critical path)                       second stream (side work, done before each join)
 //   diagnostic_update part 1 (exner, T, rho, ...)
+//   [rad, when icar_hip_rad_configure switched it on: it cools potential_temperature, which the interface values read -- the
+//    whole of part 1 runs in front of it; time_step.f90:488]
 //   [pbl, when icar_hip_pbl_configure switched it on: it reads u_mass / v_mass, so the whole of part 1 runs in front of it]
 //   mp(subset=1) interior                                 mp(halo=1) strips -> halo_send (pack + RCCL)   time_step.f90:512-526
 //   |                                                     interface values, mass-point winds (k_diag_face)
@@ -202,6 +204,7 @@ bool icar_substep_can_open_early(icar_hip_ctx *c)
 {
     const icar_hip_step_config &g = c->step.cfg;
     if (c->step.boundarylayer == ICAR_PBL_SIMPLE) return false;                   // pbl(domain, options, dt) opens the sub-step and takes dt
+    if (c->step.radiation == ICAR_RA_SIMPLE) return false;                        // rad(domain, options, dt) likewise
     return g.microphysics != 0 && g.halo_size == 1 && g.mp_update_interval == 0.0f && c->step.mp_last_model_time != -999.0
         && g.prefetch_dt && (g.cfl_strictness == 3 || g.cfl_strictness == 4) && icar_cfl_prefetch_waiting(c) && !c->on_aux;
 }
@@ -210,18 +213,19 @@ bool icar_substep_can_open_early(icar_hip_ctx *c)
 // icar_hip_step / _step_n run many sub-steps inside one library call, and the host cannot look between them: temperature,
 // density, the interface values, the mass-point winds and w_real of a sub-step that is not the call's last are seen by nobody
 // unless something on the device reads them before the next diagnostic_update rewrites them.  Who reads what:
-//   exner                 every microphysics scheme                                   -> always written
+//   exner                 every microphysics scheme, ra_simple                        -> always written
 //   density               mp_simple, WSM6, WSM3, pbl_simple, the Courant winds with advect_density
 //   temperature           the interface kernel only (k_diag_face)
 //   u_mass, v_mass, interface values   pbl_simple, the column integrals
 //   w_real                WSM3
 // Returns what the cell kernel of such a sub-step stores (ICAR_DIAG_EXNER / ICAR_DIAG_EXNER_RHO; its face kernel and w_real are
-// then left out), or 0: everything, as a single sub-step does.  When in doubt, everything.
+// then left out), or 0: everything, as a single sub-step does.  When in doubt, everything (so with ra_simple on: it would do with
+// exner, but which part suffices beside each microphysics scheme has not been measured or tested).
 static int lazy_diag_part(icar_hip_ctx *c, bool last)
 {
     const icar_hip_step_config &g = c->step.cfg;
     if (last || !g.diagnostics) return 0;
-    if (c->step.boundarylayer == ICAR_PBL_SIMPLE || g.advect_density || icar_diag_columns_on(c)) return 0;
+    if (c->step.boundarylayer == ICAR_PBL_SIMPLE || c->step.radiation == ICAR_RA_SIMPLE || g.advect_density || icar_diag_columns_on(c)) return 0;
     if (g.microphysics == kMP_THOMPSON) return ICAR_DIAG_EXNER;                                   // reads exner, p, th, dz
     if (g.microphysics == kMP_SB04 || g.microphysics == kMP_WSM6) return ICAR_DIAG_EXNER_RHO;     // ... and density
     return 0;                                                                                     // WSM3 (w_real, density), no microphysics
@@ -294,7 +298,7 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
     const float dtf = (float)dt;
     const bool adv = (g.advection == ICAR_ADV_UPWIND || g.advection == ICAR_ADV_MPDATA);
     const bool stepping = dt > 1e-3;                                              // :483
-    const bool pbl = c->step.boundarylayer == ICAR_PBL_SIMPLE;
+    const bool pbl = c->step.boundarylayer == ICAR_PBL_SIMPLE, rad = c->step.radiation == ICAR_RA_SIMPLE;
     bool wreal_later = false, face_later = false, wreal_done = false;
     const bool early = c->step.early_open;
     c->step.early_open = false;
@@ -319,7 +323,9 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
             } else {
             // exner / T / density now; the interface values and mass-point winds (nothing the microphysics reads or writes)
             // beside the interior launch below
-            face_later = stepping && g.microphysics != 0 && !pbl;                 // (simple_pbl reads u_mass and v_mass: nothing of part 1 can wait)
+            // (simple_pbl reads u_mass and v_mass, ra_simple rewrites the potential_temperature the interface values are made of:
+            // nothing of part 1 can wait)
+            face_later = stepping && g.microphysics != 0 && !pbl && !rad;
             if (icar_diagnostic_update_run(c, face_later ? ICAR_DIAG_CELL : 1)) return 1;
             if (stepping) wreal_later = true;                                     // beside the advection, below
             else if (icar_diagnostic_update_run(c, 2)) return 1;
@@ -327,6 +333,7 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
         } else if (icar_diagnostic_update_run(c, 3)) return 1;
     }
     if (!stepping) return 0;
+    if (rad && icar_rad_run(c, dtf)) return 1;                                    // :488 rad(domain, options, real(dt%seconds()))
     if (pbl && icar_pbl_run(c, dtf)) return 1;                                    // :494 pbl(domain, options, real(dt%seconds()))
 
     // :512-526  mp(halo=1) -> halo_send -> mp(subset=1) -> halo_retrieve
@@ -503,6 +510,36 @@ int icar_hip_pbl(icar_hip_ctx *c, float dt)
     if (!cfg_ok(c, "pbl")) return 1;
     HIPCHK(hipSetDevice(c->device));
     return icar_pbl_run(c, dt);
+}
+
+int icar_hip_rad_configure(icar_hip_ctx *c, int radiation)
+{
+    // the value is looked at first: a host learns that RRTMG is not built without a device
+    if (radiation == 3) { icar_set_error("rad_configure: radiation = 3 (kRA_RRTMG) is not built; 0, 1 (kRA_BASIC, nothing runs) or 2 (kRA_SIMPLE)"); return 1; }
+    if (radiation < 0 || radiation > 3) { icar_set_error("rad_configure: radiation is 0, 1 (kRA_BASIC, nothing runs) or 2 (kRA_SIMPLE)"); return 1; }
+    if (!c) { icar_set_error("rad_configure: null ctx"); return 1; }
+    c->step.radiation = radiation;
+    c->ra_lat_valid = false;                                                      // ra_simple_init: cos_lat_m / sin_lat_m are made again
+    return 0;
+}
+
+int icar_hip_rad_calendar(icar_hip_ctx *c, int calendar, double year_start_seconds, double year_days, double next_year_days)
+{
+    if (calendar < 0 || calendar > 2) { icar_set_error("rad_calendar: calendar is 0 (gregorian), 1 (noleap) or 2 (360-day)"); return 1; }
+    if (!(year_days > 0) || !(next_year_days > 0)) { icar_set_error("rad_calendar: the lengths of the year and of the next one are positive numbers of days"); return 1; }
+    if (!c) { icar_set_error("rad_calendar: null ctx"); return 1; }
+    c->step.rad_calendar = calendar; c->step.rad_year_start = year_start_seconds;
+    c->step.rad_year_days = year_days; c->step.rad_next_year_days = next_year_days;
+    c->step.rad_calendar_set = true;
+    return 0;
+}
+
+int icar_hip_rad(icar_hip_ctx *c, float dt)
+{
+    if (!c) { icar_set_error("rad: null argument"); return 1; }
+    if (!cfg_ok(c, "rad")) return 1;
+    HIPCHK(hipSetDevice(c->device));
+    return icar_rad_run(c, dt);
 }
 
 int icar_hip_mp(icar_hip_ctx *c, double dt, int halo, int subset)

@@ -21,7 +21,8 @@ module icar_hip
             hip_step_config_t, hip_step_configure, hip_update_dt, hip_compute_dt, hip_substep, hip_step, hip_step_n, hip_mp, hip_advect_step, hip_mp_reset, &
             hip_model_time, hip_set_model_time, hip_comm_unique_id, hip_comm_init, hip_comm_init_local, hip_comm_init_host, hip_comm_destroy, &
             hip_halo_send, hip_halo_retrieve, hip_co_min, hip_comm_ranks, hip_halo_selfcheck, hip_update_winds, hip_exchange_uv, hip_mpdata_exact, &
-            hip_pbl_configure, hip_pbl, hip_pbl_simple, ICAR_PBL_SIMPLE, ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_SELF, ICAR_N_ADVECTABLE
+            hip_pbl_configure, hip_pbl, hip_pbl_simple, ICAR_PBL_SIMPLE, hip_rad_configure, hip_rad_calendar, hip_rad, hip_ra_simple, ICAR_RA_SIMPLE, &
+            ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_SELF, ICAR_N_ADVECTABLE
   public :: ICAR_F_WATER_VAPOR, ICAR_F_CLOUD_WATER, ICAR_F_RAIN, ICAR_F_SNOW, ICAR_F_POTENTIAL_TEMPERATURE, &
             ICAR_F_CLOUD_ICE, ICAR_F_GRAUPEL, ICAR_F_ICE_NUMBER, ICAR_F_RAIN_NUMBER, ICAR_F_U, ICAR_F_V, ICAR_F_W, &
             ICAR_F_PRESSURE, ICAR_F_EXNER, ICAR_F_DENSITY, ICAR_F_DZ_MASS, ICAR_F_JACOBIAN, ICAR_F_JACOBIAN_U, &
@@ -29,7 +30,7 @@ module icar_hip
             ICAR_F_Z, ICAR_F_NSQUARED, ICAR_F_PRESSURE_INTERFACE, ICAR_F_TEMPERATURE, ICAR_F_TEMPERATURE_INTERFACE, &
             ICAR_F_U_MASS, ICAR_F_V_MASS, ICAR_F_W_REAL, ICAR_F_DZDX, ICAR_F_DZDY, ICAR_F_SURFACE_PRESSURE, &
             ICAR_F_IVT, ICAR_F_IWV, ICAR_F_IWL, ICAR_F_IWI, ICAR_F_ZR_U, ICAR_F_ZR_V, ICAR_F_SINTHETA, ICAR_F_COSTHETA, &
-            ICAR_F_TERRAIN, ICAR_F_LAND_MASK
+            ICAR_F_TERRAIN, ICAR_F_LAND_MASK, ICAR_F_LATITUDE, ICAR_F_LONGITUDE, ICAR_F_SHORTWAVE, ICAR_F_LONGWAVE, ICAR_F_CLOUD_FRACTION
 
   ! enum icar_hip_field (include/icar_hip.h)
   integer(c_int), parameter :: ICAR_F_WATER_VAPOR=0, ICAR_F_CLOUD_WATER=1, ICAR_F_RAIN=2, ICAR_F_SNOW=3, &
@@ -39,10 +40,12 @@ module icar_hip
        ICAR_F_PRECIPITATION=23, ICAR_F_SNOWFALL=24, ICAR_F_GRAUPEL_ACC=25, ICAR_F_PRESSURE_INTERFACE=26, ICAR_F_TEMPERATURE=27, &
        ICAR_F_TEMPERATURE_INTERFACE=28, ICAR_F_U_MASS=29, ICAR_F_V_MASS=30, ICAR_F_W_REAL=31, ICAR_F_DZDX=32, ICAR_F_DZDY=33, &
        ICAR_F_SURFACE_PRESSURE=34, ICAR_F_Z=35, ICAR_F_NSQUARED=36, ICAR_F_IVT=37, ICAR_F_IWV=38, ICAR_F_IWL=39, ICAR_F_IWI=40, &
-       ICAR_F_ZR_U=41, ICAR_F_ZR_V=42, ICAR_F_SINTHETA=43, ICAR_F_COSTHETA=44, ICAR_F_TERRAIN=45, ICAR_F_LAND_MASK=46
+       ICAR_F_ZR_U=41, ICAR_F_ZR_V=42, ICAR_F_SINTHETA=43, ICAR_F_COSTHETA=44, ICAR_F_TERRAIN=45, ICAR_F_LAND_MASK=46, &
+       ICAR_F_LATITUDE=47, ICAR_F_LONGITUDE=48, ICAR_F_SHORTWAVE=49, ICAR_F_LONGWAVE=50, ICAR_F_CLOUD_FRACTION=51
 
   integer(c_int), parameter :: ICAR_N_ADVECTABLE = 11, ICAR_NEIGHBOR_NONE = -1, ICAR_NEIGHBOR_SELF = -2
   integer(c_int), parameter :: ICAR_PBL_SIMPLE = 2      ! kPBL_SIMPLE, icar_constants.f90:355
+  integer(c_int), parameter :: ICAR_RA_SIMPLE = 2       ! kRA_SIMPLE, icar_constants.f90
 
   !> struct icar_hip_step_config == the members of options_t / grid_t the sub-step loop reads (time_step.f90:440-551)
   type, bind(C) :: hip_step_config_t
@@ -142,6 +145,18 @@ module icar_hip
        import; type(c_ptr), value :: ctx; integer(c_int), value :: boundarylayer
      end function
      integer(c_int) function icar_hip_pbl(ctx, dt) bind(C, name="icar_hip_pbl")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt
+     end function
+     integer(c_int) function icar_hip_ra_simple(ctx, dt, its, ite, jts, jte, kts, kte, runlw) bind(C, name="icar_hip_ra_simple")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt; integer(c_int), value :: its, ite, jts, jte, kts, kte, runlw
+     end function
+     integer(c_int) function icar_hip_rad_configure(ctx, radiation) bind(C, name="icar_hip_rad_configure")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: radiation
+     end function
+     integer(c_int) function icar_hip_rad_calendar(ctx, calendar, year_start_seconds, year_days, next_year_days) bind(C, name="icar_hip_rad_calendar")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: calendar; real(c_double), value :: year_start_seconds, year_days, next_year_days
+     end function
+     integer(c_int) function icar_hip_rad(ctx, dt) bind(C, name="icar_hip_rad")
        import; type(c_ptr), value :: ctx; real(c_float), value :: dt
      end function
      integer(c_int) function icar_hip_wsm6_init(ctx) bind(C, name="icar_hip_wsm6_init")
@@ -388,6 +403,40 @@ contains
     integer, intent(in) :: its, ite, jts, jte, kts, kte
     call check(icar_hip_pbl_simple(ctx%p, real(dt,c_float), int(its,c_int), int(ite,c_int), int(jts,c_int), int(jte,c_int), &
                                    int(kts,c_int), int(kte,c_int)), "pbl_simple")
+  end subroutine
+
+  !> options%physics%radiation for the sub-step loop: 0, 1 (kRA_BASIC: nothing runs) or ICAR_RA_SIMPLE; 3 (RRTMG) stops
+  subroutine hip_rad_configure(ctx, radiation)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer, intent(in) :: radiation
+    call check(icar_hip_rad_configure(ctx%p, int(radiation,c_int)), "rad_configure")
+  end subroutine
+
+  !> what Time_type%day_of_year / %year_fraction (time_obj.f90:404-480) need of domain%model_time: calendar (0 gregorian,
+  !! 1 noleap, 2 360-day), the library clock's value at 1 January 00:00 of the model time's year, that year's and the next one's days
+  subroutine hip_rad_calendar(ctx, calendar, year_start_seconds, year_days, next_year_days)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer, intent(in) :: calendar
+    double precision, intent(in) :: year_start_seconds, year_days, next_year_days
+    call check(icar_hip_rad_calendar(ctx%p, int(calendar,c_int), real(year_start_seconds,c_double), real(year_days,c_double), &
+                                     real(next_year_days,c_double)), "rad_calendar")
+  end subroutine
+
+  !> rad(domain, options, dt) (ra_driver.f90:197-285) on the tile of hip_step_configure; dt = real(dt%seconds())
+  subroutine hip_rad(ctx, dt)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    call check(icar_hip_rad(ctx%p, real(dt,c_float)), "rad")
+  end subroutine
+
+  !> ra_simple (ra_simple.f90:191-272) on the context's fields; ICAR_F_LATITUDE / ICAR_F_LONGITUDE uploaded once (hip_upload_2d)
+  subroutine hip_ra_simple(ctx, dt, its, ite, jts, jte, kts, kte, runlw)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    integer, intent(in) :: its, ite, jts, jte, kts, kte
+    logical, intent(in) :: runlw
+    call check(icar_hip_ra_simple(ctx%p, real(dt,c_float), int(its,c_int), int(ite,c_int), int(jts,c_int), int(jte,c_int), &
+                                  int(kts,c_int), int(kte,c_int), merge(1_c_int, 0_c_int, runlw)), "ra_simple")
   end subroutine
 
   subroutine hip_mp_reset(ctx)

@@ -12,6 +12,7 @@ class physics_type:                      # opt_types.f90:15-24
     windtype: int = 0
     boundarylayer: int = 0               # 0, kPBL_BASIC (nothing runs), kPBL_SIMPLE (icar_amd.pbl)
     landsurface: int = 0                 # (read by pbl_var_request only, as in the reference)
+    radiation: int = 0                   # 0, kRA_BASIC (nothing runs), kRA_SIMPLE (icar_amd.radiation)
 
 
 @dataclass

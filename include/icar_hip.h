@@ -86,7 +86,16 @@ enum icar_hip_field {
     /* simple_pbl (src/physics/pbl_simple.f90:69-86): read-only surface description, uploaded once */
     ICAR_F_TERRAIN = 45,           /* domain%terrain%data_2d  REAL(4) (nx,ny)    */
     ICAR_F_LAND_MASK = 46,         /* domain%land_mask  INTEGER(4) (nx,ny): kLC_LAND = 1, kLC_WATER = 2 */
-    ICAR_N_FIELDS = 47
+    ICAR_N_FIELDS = 47,            /* the ids 0 .. 46 above; kept at this value for hosts that size tables of their own by it */
+    /* ra_simple (src/physics/ra_simple.f90:191-272), a block of its own behind the fields above: inputs in degrees as
+     * domain%latitude%data_2d / %longitude%data_2d hold them, uploaded once; outputs domain%shortwave / %longwave /
+     * %cloud_fraction (data_2d).  REAL(4) (nx,ny) */
+    ICAR_F_LATITUDE = 47,
+    ICAR_F_LONGITUDE = 48,
+    ICAR_F_SHORTWAVE = 49,
+    ICAR_F_LONGWAVE = 50,
+    ICAR_F_CLOUD_FRACTION = 51,
+    ICAR_N_FIELD_IDS = 52          /* every id an entry point takes is below this one */
 };
 
 enum { ICAR_ADV_UPWIND = 1, ICAR_ADV_MPDATA = 2 };   /* kADV_UPWIND / kADV_MPDATA, icar_constants.f90:341 */
@@ -224,6 +233,39 @@ int icar_hip_pbl_simple(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, 
 int icar_hip_pbl_configure(icar_hip_ctx *ctx, int boundarylayer);
 int icar_hip_pbl(icar_hip_ctx *ctx, float dt);
 int icar_hip_pbl_nsubsteps(icar_hip_ctx *ctx, int *nsubsteps, int nrows);
+
+/* ---- R1: the simple radiation scheme (src/physics/ra_simple.f90, src/physics/ra_driver.f90) --------------------------------
+ * icar_hip_ra_simple == ra_simple(theta, pii, qv, qc, qs + qi + qg, qr, p, swdown, lwdown, cloud_cover, lat, lon, date, options,
+ *     dt, ims..kme, its, ite, jts, jte, kts, kte, F_runlw) (ra_simple.f90:191-272 with calc_solar_elevation :148-189, cloudfrac
+ *     :122-146, shortwave :84-103, longwave :105-120 and relative_humidity, atm_utilities.f90:306-326) on the context's
+ *     POTENTIAL_TEMPERATURE (cooled in place when runlw), EXNER, WATER_VAPOR, CLOUD_WATER, SNOW + CLOUD_ICE + GRAUPEL (the sum
+ *     ra_driver.f90:270-272 passes), RAIN, PRESSURE, LATITUDE, LONGITUDE -> SHORTWAVE, LONGWAVE, CLOUD_FRACTION; `date` is the
+ *     library clock (icar_hip_model_time) under the anchor of icar_hip_rad_calendar.  Bit-identical to the compiled reference,
+ *     including its quirks: CLOUD_FRACTION(ims:ime, j) OUTSIDE its:ite becomes 5e-8 on every row jts..jte (cloudfrac zeroes its
+ *     whole result and then floors the whole of it, :132-139); SHORTWAVE / LONGWAVE outside its:ite are an uninitialised
+ *     function result in the reference and are left untouched here; temperature and density are not re-diagnosed after the
+ *     cooling.  T_air and rh are means over kts..kts+4: fewer than 5 levels (the reference reads out of bounds) is an error,
+ *     "ra_simple: at least 5 levels", before any launch.  cos_lat_m / sin_lat_m of ra_simple_init (:62-81) are kept in the
+ *     context and made again when the scheme is configured or LATITUDE is uploaded.
+ * icar_hip_rad_configure: options%physics%radiation -- 0, 1 (kRA_BASIC: ra_driver.f90 has no branch for it, nothing runs) or
+ *     ICAR_RA_SIMPLE = kRA_SIMPLE (icar_constants.f90); 3 (kRA_RRTMG) is refused: not built.  With the scheme configured
+ *     icar_hip_substep / _step / _step_n call rad after diagnostic_update and before pbl and the microphysics
+ *     (time_step.f90:488) when dt > 1e-3 (:483).  Kept out of icar_hip_step_config so that the struct keeps its layout.
+ * icar_hip_rad_calendar: what Time_type%day_of_year / %year_fraction (time_obj.f90:404-480) need of domain%model_time.
+ *     calendar: 0 gregorian, 1 noleap, 2 360-day; year_start_seconds: the value of the library clock at 1 January 00:00 of the
+ *     year that contains the model time; year_days / next_year_days: the lengths of that year and of the next.  At the start of
+ *     each sub-step D = (model_time - year_start_seconds) / 86400 in FP64, rolled into the next year once when D >= year_days;
+ *     day_of_year(lon) = (float)(D + (double)offset(lon)); year_fraction(lon) = (float)((D + offset) / year_days) (gregorian),
+ *     day_of_year / 365.0f (noleap), / 360.0f (360-day), then mod(., 1.0).  The reference does this sum in REAL(16) from a
+ *     modified Julian day; time_obj.f90 cannot be compiled here, so THIS PART IS NOT PINNED to the compiled reference (FP64
+ *     and REAL(16) can differ in the last bit of the REAL(4) day of the year when D + offset lies within 2^-53 of a tie).
+ * icar_hip_rad == rad(domain, options, dt) (ra_driver.f90:197-285) with the tile bounds of icar_hip_step_configure; an error
+ *     when radiation = 2 and no calendar was set. */
+enum { ICAR_RA_SIMPLE = 2 };
+int icar_hip_ra_simple(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, int jte, int kts, int kte, int runlw);
+int icar_hip_rad_configure(icar_hip_ctx *ctx, int radiation);
+int icar_hip_rad_calendar(icar_hip_ctx *ctx, int calendar, double year_start_seconds, double year_days, double next_year_days);
+int icar_hip_rad(icar_hip_ctx *ctx, float dt);
 
 /* ---- T2: CFL reduction for compute_dt (src/main/time_step.f90:217-330, cfl_strictness 3) -----
  * out = max over the tile of max(|u_i|,|u_i+1|)/dx + max(|v_j|,|v_j+1|)/dx + max(|w_k|,|w_k-1|)/dz_levels(k) */
@@ -472,7 +514,7 @@ int icar_hip_step_n(icar_hip_ctx *ctx, int nsteps, double *dt_last);
 
 /* ---- measurement helpers --------------------------------------------------------------------- */
 /* Average duration (ms) of the launches of a named kernel group since the last reset, measured
- * with HIP events on the context's stream (bench.py roofline block). group: "advect", "mp", "pbl" ... */
+ * with HIP events on the context's stream (bench.py roofline block). group: "advect", "mp", "pbl", "rad" ... */
 int icar_hip_timing_enable(icar_hip_ctx *ctx, int on);
 /* restrict the timers to a comma-separated list of groups ("advect", "advect,mp,winds"; NULL or "" = all): every timed
  * scope costs its stream two timestamped barrier packets, ~5 us -- a dozen groups per sub-step are 10 % of a small tile's step */
