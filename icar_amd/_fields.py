@@ -13,7 +13,10 @@ SINTHETA, COSTHETA = 43, 44
 TERRAIN, LAND_MASK = 45, 46
 N_FIELDS = 47                   # ICAR_N_FIELDS: the ids above
 LATITUDE, LONGITUDE, SHORTWAVE, LONGWAVE, CLOUD_FRACTION = 47, 48, 49, 50, 51      # ra_simple's block behind them
-N_FIELD_IDS = 52                # ICAR_N_FIELD_IDS: every id is below this one
+N_FIELD_IDS = 52                # ICAR_N_FIELD_IDS: the ids above
+# the surface-flux slot's block behind them (icar_amd.surface)
+ROUGHNESS_Z0, U_10M, V_10M, USTAR, SST, SKIN_TEMPERATURE, SENSIBLE_HEAT, LATENT_HEAT, QSFC, QFX, DZ_INTERFACE = range(52, 63)
+N_FIELD_SLOTS = 63              # ICAR_N_FIELD_SLOTS: every id is below this one
 
 NAMES = {
     "water_vapor": WATER_VAPOR, "cloud_water_mass": CLOUD_WATER, "rain_mass": RAIN, "snow_mass": SNOW,
@@ -27,6 +30,8 @@ NAMES = {
     "z": Z, "nsquared": NSQUARED, "ivt": IVT, "iwv": IWV, "iwl": IWL, "iwi": IWI, "zr_u": ZR_U, "zr_v": ZR_V, "sintheta": SINTHETA, "costheta": COSTHETA,
     "terrain": TERRAIN, "land_mask": LAND_MASK,
     "latitude": LATITUDE, "longitude": LONGITUDE, "shortwave": SHORTWAVE, "longwave": LONGWAVE, "cloud_fraction": CLOUD_FRACTION,
+    "roughness_z0": ROUGHNESS_Z0, "u_10m": U_10M, "v_10m": V_10M, "ustar": USTAR, "sst": SST, "skin_temperature": SKIN_TEMPERATURE,
+    "sensible_heat": SENSIBLE_HEAT, "latent_heat": LATENT_HEAT, "qsfc": QSFC, "qfx": QFX, "dz_interface": DZ_INTERFACE,
     "accumulated_precipitation": PRECIPITATION, "accumulated_snowfall": SNOWFALL, "graupel": GRAUPEL_ACC,
 }
 IS_2DD = {PRECIPITATION, SNOWFALL, GRAUPEL_ACC, SINTHETA, COSTHETA}

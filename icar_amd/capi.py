@@ -32,6 +32,7 @@ SYMBOLS = [
     "icar_hip_linwinds_perturbation_download", "icar_hip_linwinds_perturbation_upload", "icar_hip_spatial_winds",
     "icar_hip_pbl_simple", "icar_hip_pbl_configure", "icar_hip_pbl", "icar_hip_pbl_nsubsteps",
     "icar_hip_ra_simple", "icar_hip_rad_configure", "icar_hip_rad_calendar", "icar_hip_rad",
+    "icar_hip_lsm_configure", "icar_hip_diag_10m", "icar_hip_water_simple", "icar_hip_apply_fluxes", "icar_hip_lsm", "icar_hip_lsm_layers",
 ]
 
 
@@ -107,6 +108,12 @@ def lib():
         L.icar_hip_rad_configure.argtypes = [vp, ci]
         L.icar_hip_rad_calendar.argtypes = [vp, ci, ctypes.c_double, ctypes.c_double, ctypes.c_double]
         L.icar_hip_rad.argtypes = [vp, ctypes.c_float]
+        L.icar_hip_lsm_configure.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ctypes.c_float]
+        L.icar_hip_diag_10m.argtypes = [vp]
+        L.icar_hip_water_simple.argtypes = [vp]
+        L.icar_hip_apply_fluxes.argtypes = [vp, ctypes.c_float, ci, ci, ci, ci, ci, ci]
+        L.icar_hip_lsm.argtypes = [vp, ctypes.c_float]
+        L.icar_hip_lsm_layers.argtypes = [vp, ctypes.POINTER(ci)]
         _lib = L
     return _lib
 

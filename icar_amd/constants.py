@@ -14,6 +14,13 @@ kPBL_YSU = 3
 kRA_BASIC = 1                   # icar_constants.f90 (radiation)
 kRA_SIMPLE = 2
 kRA_RRTMG = 3
+kWATER_BASIC = 1                # icar_constants.f90:358-365 (water and land surface)
+kWATER_SIMPLE = 2
+kWATER_LAKE = 3
+kLSM_BASIC = 1
+kLSM_SIMPLE = 2
+kLSM_NOAH = 3
+kLSM_NOAHMP = 4
 kLC_LAND = 1                    # land_mask values, icar_constants.f90
 kLC_WATER = 2
 kDEFAULT_HALO_SIZE = 1          # icar_constants.f90:320

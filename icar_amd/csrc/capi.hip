@@ -35,13 +35,14 @@ size_t icar_field_count(const icar_hip_ctx *c, int f)
     const size_t nx = c->d.nx, nz = c->d.nz, ny = c->d.ny;
     if (f == ICAR_F_U || f == ICAR_F_JACOBIAN_U || f == ICAR_F_DZDX || f == ICAR_F_ZR_U) return (nx + 1) * nz * ny;
     if (f == ICAR_F_V || f == ICAR_F_JACOBIAN_V || f == ICAR_F_DZDY || f == ICAR_F_ZR_V) return nx * nz * (ny + 1);
-    if (field_is_2dd(f) || f == ICAR_F_SURFACE_PRESSURE || (f >= ICAR_F_IVT && f <= ICAR_F_IWI) || f >= ICAR_F_TERRAIN) return nx * ny;      // the surface fields of pbl_simple and ra_simple
+    if (f == ICAR_F_DZ_INTERFACE) return nx * nz * ny;
+    if (field_is_2dd(f) || f == ICAR_F_SURFACE_PRESSURE || (f >= ICAR_F_IVT && f <= ICAR_F_IWI) || f >= ICAR_F_TERRAIN) return nx * ny;      // the surface fields of pbl_simple, ra_simple and the surface-flux slot
     return nx * nz * ny;
 }
 
 float *icar_field_f(icar_hip_ctx *c, int f, bool required)
 {
-    if (f < 0 || f >= ICAR_N_FIELD_IDS) { icar_set_error("bad field id"); return nullptr; }
+    if (f < 0 || f >= ICAR_N_FIELD_SLOTS) { icar_set_error("bad field id"); return nullptr; }
     if (!c->field[f]) {
         if (required) {
             char b[96]; snprintf(b, sizeof b, "field %d has not been uploaded to the device", f);
@@ -137,9 +138,9 @@ int icar_hip_ctx_destroy(icar_hip_ctx *c)
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     drain_timers(c);
-    for (int f = 0; f < ICAR_N_FIELD_IDS; ++f) if (c->field[f]) hipFree(c->field[f]);
+    for (int f = 0; f < ICAR_N_FIELD_SLOTS; ++f) if (c->field[f]) hipFree(c->field[f]);
     for (int f = 0; f < ICAR_N_ADVECTABLE; ++f) if (c->alt[f]) hipFree(c->alt[f]);
-    for (int f = 0; f < ICAR_N_FIELD_IDS; ++f) if (c->dqdt[f]) hipFree(c->dqdt[f]);
+    for (int f = 0; f < ICAR_N_FIELD_SLOTS; ++f) if (c->dqdt[f]) hipFree(c->dqdt[f]);
     float *scr[] = {c->U, c->V, c->W, c->Wdz, c->d_red, c->mpc, c->mpx_buf};
     for (float *p : scr) if (p) hipFree(p);
     if (c->d_flag) hipFree(c->d_flag);
@@ -150,6 +151,7 @@ int icar_hip_ctx_destroy(icar_hip_ctx *c)
     if (c->pbl_kq) hipFree(c->pbl_kq);
     if (c->pbl_rowmax) hipFree(c->pbl_rowmax);
     if (c->ra_coslat) hipFree(c->ra_coslat);
+    if (c->sfc_levelmax) hipFree(c->sfc_levelmax);
     icar_wsm3_free(c);
     icar_wsm6_free(c);
     icar_thompson_free(c);
@@ -198,6 +200,7 @@ int icar_hip_field_upload(icar_hip_ctx *c, int f, const void *host)
     HIPCHK(hipStreamSynchronize(c->stream));
     if (field_feeds_winds(f)) icar_winds_changed(c);
     if (f == ICAR_F_LATITUDE) c->ra_lat_valid = false;
+    if (f == ICAR_F_DZ_INTERFACE) c->sfc_nz_valid = false;                        // apply_fluxes looks for nz again
     return 0;
 }
 
@@ -224,6 +227,7 @@ int icar_hip_field_fill(icar_hip_ctx *c, int f, double value)
     HIPCHK(hipGetLastError());
     if (field_feeds_winds(f)) icar_winds_changed(c);
     if (f == ICAR_F_LATITUDE) c->ra_lat_valid = false;
+    if (f == ICAR_F_DZ_INTERFACE) c->sfc_nz_valid = false;                        // apply_fluxes looks for nz again
     return 0;
 }
 
@@ -348,7 +352,7 @@ int icar_hip_diagnostic_update_parts(icar_hip_ctx *c, int parts)
 int icar_hip_dqdt_upload(icar_hip_ctx *c, int f, const void *host)
 {
     if (icar_enter(c, "dqdt_upload", host != nullptr)) return 1;
-    if (f < 0 || f >= ICAR_N_FIELD_IDS || field_is_2dd(f) || f >= ICAR_F_TERRAIN) { icar_set_error("dqdt_upload: bad field"); return 1; }
+    if (f < 0 || f >= ICAR_N_FIELD_SLOTS || field_is_2dd(f) || f >= ICAR_F_TERRAIN) { icar_set_error("dqdt_upload: bad field"); return 1; }
     const size_t bytes = icar_field_count(c, f) * sizeof(float);
     if (!c->dqdt[f]) HIPCHK(hipMalloc(&c->dqdt[f], bytes));
     HIPCHK(hipMemcpyAsync(c->dqdt[f], host, bytes, hipMemcpyHostToDevice, c->stream));
@@ -479,7 +483,7 @@ int icar_hip_box_unpack(icar_hip_ctx *c, int field, int which, int i0, int ni, i
 int icar_hip_dqdt_download(icar_hip_ctx *c, int f, void *host)
 {
     if (icar_enter(c, "dqdt_download", host != nullptr)) return 1;
-    if (f < 0 || f >= ICAR_N_FIELD_IDS || field_is_2dd(f) || !c->dqdt[f]) { icar_set_error("dqdt_download: no dqdt mirror for this field"); return 1; }
+    if (f < 0 || f >= ICAR_N_FIELD_SLOTS || field_is_2dd(f) || !c->dqdt[f]) { icar_set_error("dqdt_download: no dqdt mirror for this field"); return 1; }
     HIPCHK(hipMemcpyAsync(host, c->dqdt[f], icar_field_count(c, f) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;

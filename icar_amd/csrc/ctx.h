@@ -48,6 +48,10 @@ struct IcarStepState {
     bool rad_calendar_set = false;
     int rad_calendar = 0;
     double rad_year_start = 0.0, rad_year_days = 365.0, rad_next_year_days = 365.0;
+    // icar_hip_lsm_configure: options%physics%landsurface / %watersurface, options%lsm_options, lsm_driver.f90's SAVE variable last_model_time
+    int landsurface = 0, watersurface = 0, lsm_update_interval = 300;
+    float sh_feedback_fraction = 0.625f, lh_feedback_fraction = 1.0f, sfc_layer_thickness = 400.0f;
+    double lsm_last_model_time = -999.0;
 };
 
 // component indices of the per-cell coefficients in icar_hip_ctx::mpc (k_mpdata_coef in mpdata.hip says what they hold): the first
@@ -70,8 +74,8 @@ struct icar_hip_ctx {
     hipStream_t aux = nullptr, main_saved = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool on_aux = false;
-    void *field[ICAR_N_FIELD_IDS] = {nullptr};
-    float *dqdt[ICAR_N_FIELD_IDS] = {nullptr};    // variable_t%dqdt_3d mirrors (apply_forcing)
+    void *field[ICAR_N_FIELD_SLOTS] = {nullptr};
+    float *dqdt[ICAR_N_FIELD_SLOTS] = {nullptr};    // variable_t%dqdt_3d mirrors (apply_forcing)
     // advection scratch (A1-A5)
     float *U = nullptr, *V = nullptr, *W = nullptr, *Wdz = nullptr;
     float *mpc = nullptr;                // MPDATA: the scalar-independent coefficients of this step's winds, mpc_bytes(n3) (MPC_* above)
@@ -95,6 +99,11 @@ struct icar_hip_ctx {
     unsigned *pbl_rowmax = nullptr;      // pbl_simple.hip: bit pattern of maxval(Kq/dz) of every row (ny)
     float *ra_coslat = nullptr;          // ra_simple.hip: cos_lat_m | sin_lat_m of ra_simple_init (2 x nx*ny), allocated on first use
     bool ra_lat_valid = false;           // ... and whether they are those of the ICAR_F_LATITUDE on the device
+    // sfc_basic.hip: apply_fluxes' nz (its SAVE variable) for (kts, kte, sfc_layer_thickness), and the levels' maxima it is found from
+    bool sfc_nz_valid = false;
+    int sfc_nz = 0, sfc_nz_kts = 0, sfc_nz_kte = 0;
+    float sfc_nz_thick = 0.0f;
+    unsigned *sfc_levelmax = nullptr;
     // reductions / flags
     float *d_red = nullptr;              // small device scratch for reductions
     std::vector<float> dzl_host;         // dz_levels last uploaded behind d_red (compute_dt re-sends them only when they change)
@@ -147,6 +156,13 @@ int icar_pbl_nsubsteps_copy(icar_hip_ctx *c, int *out, int n);
 int icar_ra_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte, int runlw, int calendar, double D, double year_days);
 int icar_rad_clock(icar_hip_ctx *c, double model_time, double *D, double *year_days);   // day of the year under icar_hip_rad_calendar's anchor
 int icar_rad_run(icar_hip_ctx *c, float dt);                                // rad(domain, options, dt): the configured scheme on the step's tile
+// sfc_basic.hip
+int icar_sfc_diag_10m_run(icar_hip_ctx *c);                                 // time_step.f90:143-161
+int icar_sfc_water_simple_run(icar_hip_ctx *c);
+int icar_sfc_layers(icar_hip_ctx *c, int kts, int kte, int *nz_out);
+int icar_sfc_apply_fluxes_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);
+int icar_lsm_run(icar_hip_ctx *c, float dt);                                // lsm(domain, options, dt): the gate, water_simple, apply_fluxes on the step's tile
+int icar_lsm_init_device(icar_hip_ctx *c);
 // timestep.hip
 int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset);      // halo / subset < 0: argument not present
 int icar_update_dt(icar_hip_ctx *c, double *seconds);

@@ -95,7 +95,7 @@ __global__ void k_box(int X, int nz, int i0, int ni, int j0, int nj, float *__re
 
 int icar_box_copy(icar_hip_ctx *c, int field, int which, int i0, int ni, int j0, int nj, float *buf, bool unpack)
 {
-    if (field < 0 || field >= ICAR_N_FIELD_IDS || icar_hip_field_elem_size(field) != 4) { icar_set_error("box: REAL(4) fields only"); return 1; }
+    if (field < 0 || field >= ICAR_N_FIELD_SLOTS || icar_hip_field_elem_size(field) != 4) { icar_set_error("box: REAL(4) fields only"); return 1; }
     const int nx = c->d.nx, nz = c->d.nz, ny = c->d.ny;
     if (icar_field_count(c, field) < (size_t)nx * nz * ny) { icar_set_error("box: 3-D fields only"); return 1; }
     const int X = (field == ICAR_F_U || field == ICAR_F_JACOBIAN_U || field == ICAR_F_DZDX || field == ICAR_F_ZR_U) ? nx + 1 : nx;

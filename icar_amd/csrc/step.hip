@@ -255,6 +255,8 @@ int icar_diagnostic_update_run(icar_hip_ctx *c, int parts)
     if (columns ? (parts & ICAR_DIAG_CELL) : (parts & ICAR_DIAG_FACE)) {          // (with column integrals: at the CELL call)
         dim3 g((c->d.nx + 63) / 64, (c->d.nz + 3) / 4, c->d.ny), b(64, 4);
         hipLaunchKernelGGL(k_diag_face, g, b, 0, c->stream, c->d, p, T, pi, ps, Ti, u, v, um, vm);
+        // :143-161 the 10 m winds and ustar behind the mass-point winds, `if (associated(domain%roughness_z0%data_2d))`
+        if (c->field[ICAR_F_ROUGHNESS_Z0] && icar_sfc_diag_10m_run(c)) return 1;
     }
     if (columns && (parts & ICAR_DIAG_CELL)) {
         ca.qv = (const float *)c->field[ICAR_F_WATER_VAPOR]; ca.um = um; ca.vm = vm; ca.p_i = pi;
@@ -288,7 +290,7 @@ int icar_apply_forcing_run(icar_hip_ctx *c, double dt, const int *fields, const 
     ForceArgs a;
     for (int m = 0; m < n; ++m) {
         const int f = fields[m];
-        if (f < 0 || f >= ICAR_N_FIELD_IDS || f == ICAR_F_PRECIPITATION || f == ICAR_F_SNOWFALL || f == ICAR_F_GRAUPEL_ACC || f == ICAR_F_SURFACE_PRESSURE || f >= ICAR_F_TERRAIN) {
+        if (f < 0 || f >= ICAR_N_FIELD_SLOTS || f == ICAR_F_PRECIPITATION || f == ICAR_F_SNOWFALL || f == ICAR_F_GRAUPEL_ACC || f == ICAR_F_SURFACE_PRESSURE || f >= ICAR_F_TERRAIN) {
             icar_set_error("apply_forcing: only 3-D REAL(4) fields"); return 1;
         }
         a.x[m] = icar_field_f(c, f);

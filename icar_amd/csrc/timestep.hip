@@ -9,6 +9,8 @@
 //   diagnostic_update part 1 (exner, T, rho, ...)
 //   [rad, when icar_hip_rad_configure switched it on: it cools potential_temperature, which the interface values read -- the
 //    whole of part 1 runs in front of it; time_step.f90:488]
+//   [lsm, when icar_hip_lsm_configure switched it on: it reads the 10 m winds, which follow the mass-point winds -- the whole of
+//    part 1 runs in front of it; time_step.f90:491]
 //   [pbl, when icar_hip_pbl_configure switched it on: it reads u_mass / v_mass, so the whole of part 1 runs in front of it]
 //   mp(subset=1) interior                                 mp(halo=1) strips -> halo_send (pack + RCCL)   time_step.f90:512-526
 //   |                                                     interface values, mass-point winds (k_diag_face)
@@ -205,6 +207,7 @@ bool icar_substep_can_open_early(icar_hip_ctx *c)
     const icar_hip_step_config &g = c->step.cfg;
     if (c->step.boundarylayer == ICAR_PBL_SIMPLE) return false;                   // pbl(domain, options, dt) opens the sub-step and takes dt
     if (c->step.radiation == ICAR_RA_SIMPLE) return false;                        // rad(domain, options, dt) likewise
+    if (c->step.landsurface != 0) return false;                                   // lsm(domain, options, dt) likewise
     return g.microphysics != 0 && g.halo_size == 1 && g.mp_update_interval == 0.0f && c->step.mp_last_model_time != -999.0
         && g.prefetch_dt && (g.cfl_strictness == 3 || g.cfl_strictness == 4) && icar_cfl_prefetch_waiting(c) && !c->on_aux;
 }
@@ -226,6 +229,7 @@ static int lazy_diag_part(icar_hip_ctx *c, bool last)
     const icar_hip_step_config &g = c->step.cfg;
     if (last || !g.diagnostics) return 0;
     if (c->step.boundarylayer == ICAR_PBL_SIMPLE || c->step.radiation == ICAR_RA_SIMPLE || g.advect_density || icar_diag_columns_on(c)) return 0;
+    if (c->step.landsurface != 0) return 0;                                       // lsm reads temperature, density, the 10 m winds and ustar
     if (g.microphysics == kMP_THOMPSON) return ICAR_DIAG_EXNER;                                   // reads exner, p, th, dz
     if (g.microphysics == kMP_SB04 || g.microphysics == kMP_WSM6) return ICAR_DIAG_EXNER_RHO;     // ... and density
     return 0;                                                                                     // WSM3 (w_real, density), no microphysics
@@ -298,7 +302,7 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
     const float dtf = (float)dt;
     const bool adv = (g.advection == ICAR_ADV_UPWIND || g.advection == ICAR_ADV_MPDATA);
     const bool stepping = dt > 1e-3;                                              // :483
-    const bool pbl = c->step.boundarylayer == ICAR_PBL_SIMPLE, rad = c->step.radiation == ICAR_RA_SIMPLE;
+    const bool pbl = c->step.boundarylayer == ICAR_PBL_SIMPLE, rad = c->step.radiation == ICAR_RA_SIMPLE, lsm = c->step.landsurface != 0;
     bool wreal_later = false, face_later = false, wreal_done = false;
     const bool early = c->step.early_open;
     c->step.early_open = false;
@@ -325,7 +329,8 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
             // beside the interior launch below
             // (simple_pbl reads u_mass and v_mass, ra_simple rewrites the potential_temperature the interface values are made of:
             // nothing of part 1 can wait)
-            face_later = stepping && g.microphysics != 0 && !pbl && !rad;
+            // (lsm reads u_10m, v_10m and ustar, which are made behind the mass-point winds)
+            face_later = stepping && g.microphysics != 0 && !pbl && !rad && !lsm;
             if (icar_diagnostic_update_run(c, face_later ? ICAR_DIAG_CELL : 1)) return 1;
             if (stepping) wreal_later = true;                                     // beside the advection, below
             else if (icar_diagnostic_update_run(c, 2)) return 1;
@@ -334,6 +339,7 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
     }
     if (!stepping) return 0;
     if (rad && icar_rad_run(c, dtf)) return 1;                                    // :488 rad(domain, options, real(dt%seconds()))
+    if (lsm && icar_lsm_run(c, dtf)) return 1;                                    // :491 lsm(domain, options, real(dt%seconds()))
     if (pbl && icar_pbl_run(c, dtf)) return 1;                                    // :494 pbl(domain, options, real(dt%seconds()))
 
     // :512-526  mp(halo=1) -> halo_send -> mp(subset=1) -> halo_retrieve
@@ -540,6 +546,61 @@ int icar_hip_rad(icar_hip_ctx *c, float dt)
     if (!cfg_ok(c, "rad")) return 1;
     HIPCHK(hipSetDevice(c->device));
     return icar_rad_run(c, dt);
+}
+
+int icar_hip_lsm_configure(icar_hip_ctx *c, int landsurface, int watersurface, int update_interval, float sh_feedback_fraction,
+                           float lh_feedback_fraction, float sfc_layer_thickness)
+{
+    // the values are looked at first: a host learns what is not built without a device
+    if (landsurface == 2) { icar_set_error("lsm_configure: landsurface = 2 (kLSM_SIMPLE): the reference stops here with \"Simple LSM not settup, choose a different LSM options\" (lsm_driver.f90:615); 0 or 1 (kLSM_BASIC)"); return 1; }
+    if (landsurface == 3) { icar_set_error("lsm_configure: landsurface = 3 (kLSM_NOAH) is not built; 0 or 1 (kLSM_BASIC)"); return 1; }
+    if (landsurface == 4) { icar_set_error("lsm_configure: landsurface = 4 (kLSM_NOAHMP) is not built; 0 or 1 (kLSM_BASIC)"); return 1; }
+    if (landsurface < 0 || landsurface > 4) { icar_set_error("lsm_configure: landsurface is 0 or 1 (kLSM_BASIC)"); return 1; }
+    if (watersurface == 3) { icar_set_error("lsm_configure: watersurface = 3 (kWATER_LAKE) is not built; 0, 1 (kWATER_BASIC, nothing runs) or 2 (kWATER_SIMPLE)"); return 1; }
+    if (watersurface < 0 || watersurface > 3) { icar_set_error("lsm_configure: watersurface is 0, 1 (kWATER_BASIC, nothing runs) or 2 (kWATER_SIMPLE)"); return 1; }
+    if (update_interval < 0 || !(sfc_layer_thickness > 0)) { icar_set_error("lsm_configure: update_interval >= 0 seconds and a positive sfc_layer_thickness"); return 1; }
+    if (!c) { icar_set_error("lsm_configure: null ctx"); return 1; }
+    IcarStepState &s = c->step;
+    s.landsurface = landsurface; s.watersurface = watersurface; s.lsm_update_interval = update_interval;
+    s.sh_feedback_fraction = sh_feedback_fraction; s.lh_feedback_fraction = lh_feedback_fraction; s.sfc_layer_thickness = sfc_layer_thickness;
+    s.lsm_last_model_time = -999.0;                                               // lsm_driver.f90:1000
+    c->sfc_nz_valid = false;                                                      // apply_fluxes' SAVE variable nz
+    HIPCHK(hipSetDevice(c->device));
+    return icar_lsm_init_device(c);
+}
+
+int icar_hip_diag_10m(icar_hip_ctx *c)
+{
+    if (icar_enter(c, "diag_10m")) return 1;
+    return icar_sfc_diag_10m_run(c);
+}
+
+int icar_hip_water_simple(icar_hip_ctx *c)
+{
+    if (icar_enter(c, "water_simple")) return 1;
+    return icar_sfc_water_simple_run(c);
+}
+
+int icar_hip_apply_fluxes(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte)
+{
+    if (icar_enter(c, "apply_fluxes")) return 1;
+    return icar_sfc_apply_fluxes_run(c, dt, its, ite, jts, jte, kts, kte);
+}
+
+int icar_hip_lsm(icar_hip_ctx *c, float dt)
+{
+    if (!c) { icar_set_error("lsm: null argument"); return 1; }
+    if (!cfg_ok(c, "lsm")) return 1;
+    HIPCHK(hipSetDevice(c->device));
+    return icar_lsm_run(c, dt);
+}
+
+int icar_hip_lsm_layers(icar_hip_ctx *c, int *nz)
+{
+    if (!c || !nz) { icar_set_error("lsm_layers: null argument"); return 1; }
+    if (!cfg_ok(c, "lsm_layers")) return 1;
+    HIPCHK(hipSetDevice(c->device));
+    return icar_sfc_layers(c, c->step.cfg.kts, c->step.cfg.kte, nz);
 }
 
 int icar_hip_mp(icar_hip_ctx *c, double dt, int halo, int subset)

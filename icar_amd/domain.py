@@ -32,6 +32,7 @@ class domain_t:
         self._step_key = None            # what the library's step driver was last configured with (configure())
         self._pbl_key = 0                # options%physics%boundarylayer as last handed to icar_hip_pbl_configure
         self._rad_key = 0                # options%physics%radiation as last handed to icar_hip_rad_configure
+        self._lsm_key = (0, 0)           # options%physics%landsurface / %watersurface and lsm_options as last handed to icar_hip_lsm_configure
         self._forced, self._diagnostics, self._prefetch_dt = (), True, True
         if comm is not None:
             comm.attach(self)            # icar_hip_comm_init[_host]: collective over the images of the communicator
@@ -52,14 +53,17 @@ class domain_t:
     def model_time_seconds(self, seconds):
         check(lib().icar_hip_model_time_set(self.ctx, float(seconds)), "icar_hip_model_time_set")
 
-    def configure(self, options, forced=None, diagnostics=None, prefetch_dt=None, advection=None, boundarylayer=None, radiation=None):
+    def configure(self, options, forced=None, diagnostics=None, prefetch_dt=None, advection=None, boundarylayer=None, radiation=None,
+                  landsurface=None, watersurface=None):
         """icar_hip_step_configure: hand the library the members of options_t / grid_t that step(), update_dt(), mp() and
         advect() read (time_step.f90:440-551).  Cheap when nothing changed.  forced = [(member, force_boundaries), ...] (the
         variables apply_forcing updates), diagnostics (diagnostic_update at the top of a sub-step) and prefetch_dt stay as last
         given when omitted.  advection=0 overrides options%physics%advection (time_step.mp_and_halo: the microphysics + halo
         block alone), boundarylayer=0 likewise options%physics%boundarylayer (handed to icar_hip_pbl_configure: pbl() then runs
         between diagnostic_update and the microphysics of every sub-step), radiation=0 options%physics%radiation
-        (icar_hip_rad_configure: rad() then runs in front of pbl(); the calendar anchor is icar_amd.radiation.rad_calendar's)."""
+        (icar_hip_rad_configure: rad() then runs in front of pbl(); the calendar anchor is icar_amd.radiation.rad_calendar's),
+        landsurface=0 / watersurface=0 options%physics%landsurface / %watersurface (icar_hip_lsm_configure with options%lsm_options:
+        lsm() then runs between rad() and pbl(); handed over only when they change, since that resets lsm's update gate)."""
         p, g = options.parameters, self.grid
         bl = int(options.physics.boundarylayer if boundarylayer is None else boundarylayer)
         if bl != self._pbl_key:
@@ -69,6 +73,14 @@ class domain_t:
         if ra != self._rad_key:
             check(lib().icar_hip_rad_configure(self.ctx, ra), "icar_hip_rad_configure")
             self._rad_key = ra
+        lo = getattr(options, "lsm_options", None)
+        ls = int(getattr(options.physics, "landsurface", 0) if landsurface is None else landsurface)
+        ws = int(getattr(options.physics, "watersurface", 0) if watersurface is None else watersurface)
+        lkey = (ls, ws) if ls == 0 or lo is None else (ls, ws, int(lo.update_interval), float(lo.sh_feedback_fraction), float(lo.lh_feedback_fraction), float(lo.sfc_layer_thickness))
+        if lkey != self._lsm_key and not (ls == 0 and self._lsm_key[0] == 0):
+            from .surface import lsm_configure
+            if ls == 0 or lo is None: lsm_configure(self, ls, ws)
+            else: lsm_configure(self, *lkey)
         adv = options.physics.advection if advection is None else advection
         adv_ids = tuple(KVARS[n][0] for n in ADVECTION_ORDER if options.vars_to_advect.get(n, 0) > 0)
         if forced is not None: self._forced = tuple((self.fid(n), int(bool(b))) for n, b in forced)
@@ -121,6 +133,7 @@ class domain_t:
     def shape(self, fid):
         if fid in (F.U, F.JACOBIAN_U, F.DZDX, F.ZR_U): return (self.ny, self.nz, self.nx + 1)
         if fid in (F.V, F.JACOBIAN_V, F.DZDY, F.ZR_V): return (self.ny + 1, self.nz, self.nx)
+        if fid == F.DZ_INTERFACE: return (self.ny, self.nz, self.nx)
         if fid in F.IS_2DD or fid in (F.SURFACE_PRESSURE, F.IVT, F.IWV, F.IWL, F.IWI) or fid >= F.TERRAIN: return (self.ny, self.nx)
         return (self.ny, self.nz, self.nx)
 

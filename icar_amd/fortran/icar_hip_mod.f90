@@ -22,6 +22,7 @@ module icar_hip
             hip_model_time, hip_set_model_time, hip_comm_unique_id, hip_comm_init, hip_comm_init_local, hip_comm_init_host, hip_comm_destroy, &
             hip_halo_send, hip_halo_retrieve, hip_co_min, hip_comm_ranks, hip_halo_selfcheck, hip_update_winds, hip_exchange_uv, hip_mpdata_exact, &
             hip_pbl_configure, hip_pbl, hip_pbl_simple, ICAR_PBL_SIMPLE, hip_rad_configure, hip_rad_calendar, hip_rad, hip_ra_simple, ICAR_RA_SIMPLE, &
+            hip_lsm_configure, hip_diag_10m, hip_water_simple, hip_apply_fluxes, hip_lsm, hip_lsm_layers, ICAR_LSM_BASIC, ICAR_WATER_SIMPLE, &
             ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_SELF, ICAR_N_ADVECTABLE
   public :: ICAR_F_WATER_VAPOR, ICAR_F_CLOUD_WATER, ICAR_F_RAIN, ICAR_F_SNOW, ICAR_F_POTENTIAL_TEMPERATURE, &
             ICAR_F_CLOUD_ICE, ICAR_F_GRAUPEL, ICAR_F_ICE_NUMBER, ICAR_F_RAIN_NUMBER, ICAR_F_U, ICAR_F_V, ICAR_F_W, &
@@ -30,7 +31,9 @@ module icar_hip
             ICAR_F_Z, ICAR_F_NSQUARED, ICAR_F_PRESSURE_INTERFACE, ICAR_F_TEMPERATURE, ICAR_F_TEMPERATURE_INTERFACE, &
             ICAR_F_U_MASS, ICAR_F_V_MASS, ICAR_F_W_REAL, ICAR_F_DZDX, ICAR_F_DZDY, ICAR_F_SURFACE_PRESSURE, &
             ICAR_F_IVT, ICAR_F_IWV, ICAR_F_IWL, ICAR_F_IWI, ICAR_F_ZR_U, ICAR_F_ZR_V, ICAR_F_SINTHETA, ICAR_F_COSTHETA, &
-            ICAR_F_TERRAIN, ICAR_F_LAND_MASK, ICAR_F_LATITUDE, ICAR_F_LONGITUDE, ICAR_F_SHORTWAVE, ICAR_F_LONGWAVE, ICAR_F_CLOUD_FRACTION
+            ICAR_F_TERRAIN, ICAR_F_LAND_MASK, ICAR_F_LATITUDE, ICAR_F_LONGITUDE, ICAR_F_SHORTWAVE, ICAR_F_LONGWAVE, ICAR_F_CLOUD_FRACTION, &
+            ICAR_F_ROUGHNESS_Z0, ICAR_F_U_10M, ICAR_F_V_10M, ICAR_F_USTAR, ICAR_F_SST, ICAR_F_SKIN_TEMPERATURE, ICAR_F_SENSIBLE_HEAT, &
+            ICAR_F_LATENT_HEAT, ICAR_F_QSFC, ICAR_F_QFX, ICAR_F_DZ_INTERFACE
 
   ! enum icar_hip_field (include/icar_hip.h)
   integer(c_int), parameter :: ICAR_F_WATER_VAPOR=0, ICAR_F_CLOUD_WATER=1, ICAR_F_RAIN=2, ICAR_F_SNOW=3, &
@@ -41,10 +44,13 @@ module icar_hip
        ICAR_F_TEMPERATURE_INTERFACE=28, ICAR_F_U_MASS=29, ICAR_F_V_MASS=30, ICAR_F_W_REAL=31, ICAR_F_DZDX=32, ICAR_F_DZDY=33, &
        ICAR_F_SURFACE_PRESSURE=34, ICAR_F_Z=35, ICAR_F_NSQUARED=36, ICAR_F_IVT=37, ICAR_F_IWV=38, ICAR_F_IWL=39, ICAR_F_IWI=40, &
        ICAR_F_ZR_U=41, ICAR_F_ZR_V=42, ICAR_F_SINTHETA=43, ICAR_F_COSTHETA=44, ICAR_F_TERRAIN=45, ICAR_F_LAND_MASK=46, &
-       ICAR_F_LATITUDE=47, ICAR_F_LONGITUDE=48, ICAR_F_SHORTWAVE=49, ICAR_F_LONGWAVE=50, ICAR_F_CLOUD_FRACTION=51
+       ICAR_F_LATITUDE=47, ICAR_F_LONGITUDE=48, ICAR_F_SHORTWAVE=49, ICAR_F_LONGWAVE=50, ICAR_F_CLOUD_FRACTION=51, &
+       ICAR_F_ROUGHNESS_Z0=52, ICAR_F_U_10M=53, ICAR_F_V_10M=54, ICAR_F_USTAR=55, ICAR_F_SST=56, ICAR_F_SKIN_TEMPERATURE=57, &
+       ICAR_F_SENSIBLE_HEAT=58, ICAR_F_LATENT_HEAT=59, ICAR_F_QSFC=60, ICAR_F_QFX=61, ICAR_F_DZ_INTERFACE=62
 
   integer(c_int), parameter :: ICAR_N_ADVECTABLE = 11, ICAR_NEIGHBOR_NONE = -1, ICAR_NEIGHBOR_SELF = -2
   integer(c_int), parameter :: ICAR_PBL_SIMPLE = 2      ! kPBL_SIMPLE, icar_constants.f90:355
+  integer(c_int), parameter :: ICAR_LSM_BASIC = 1, ICAR_WATER_SIMPLE = 2     ! kLSM_BASIC, kWATER_SIMPLE, icar_constants.f90:358-365
   integer(c_int), parameter :: ICAR_RA_SIMPLE = 2       ! kRA_SIMPLE, icar_constants.f90
 
   !> struct icar_hip_step_config == the members of options_t / grid_t the sub-step loop reads (time_step.f90:440-551)
@@ -158,6 +164,26 @@ module icar_hip
      end function
      integer(c_int) function icar_hip_rad(ctx, dt) bind(C, name="icar_hip_rad")
        import; type(c_ptr), value :: ctx; real(c_float), value :: dt
+     end function
+     integer(c_int) function icar_hip_lsm_configure(ctx, landsurface, watersurface, update_interval, sh_feedback_fraction, lh_feedback_fraction, &
+                                                    sfc_layer_thickness) bind(C, name="icar_hip_lsm_configure")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: landsurface, watersurface, update_interval
+       real(c_float), value :: sh_feedback_fraction, lh_feedback_fraction, sfc_layer_thickness
+     end function
+     integer(c_int) function icar_hip_diag_10m(ctx) bind(C, name="icar_hip_diag_10m")
+       import; type(c_ptr), value :: ctx
+     end function
+     integer(c_int) function icar_hip_water_simple(ctx) bind(C, name="icar_hip_water_simple")
+       import; type(c_ptr), value :: ctx
+     end function
+     integer(c_int) function icar_hip_apply_fluxes(ctx, dt, its, ite, jts, jte, kts, kte) bind(C, name="icar_hip_apply_fluxes")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt; integer(c_int), value :: its, ite, jts, jte, kts, kte
+     end function
+     integer(c_int) function icar_hip_lsm(ctx, dt) bind(C, name="icar_hip_lsm")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt
+     end function
+     integer(c_int) function icar_hip_lsm_layers(ctx, nz) bind(C, name="icar_hip_lsm_layers")
+       import; type(c_ptr), value :: ctx; integer(c_int) :: nz
      end function
      integer(c_int) function icar_hip_wsm6_init(ctx) bind(C, name="icar_hip_wsm6_init")
        import; type(c_ptr), value :: ctx
@@ -438,6 +464,53 @@ contains
     call check(icar_hip_ra_simple(ctx%p, real(dt,c_float), int(its,c_int), int(ite,c_int), int(jts,c_int), int(jte,c_int), &
                                   int(kts,c_int), int(kte,c_int), merge(1_c_int, 0_c_int, runlw)), "ra_simple")
   end subroutine
+
+  !> lsm_init (lsm_driver.f90:522-611, :991-1000): options%physics%landsurface (0 or ICAR_LSM_BASIC; 2 stops as the reference does,
+  !! 3 and 4 are not built), %watersurface (0, 1 or ICAR_WATER_SIMPLE; 3 is not built) and options%lsm_options; resets the update gate
+  subroutine hip_lsm_configure(ctx, landsurface, watersurface, update_interval, sh_feedback_fraction, lh_feedback_fraction, sfc_layer_thickness)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer, intent(in) :: landsurface, watersurface, update_interval
+    real, intent(in) :: sh_feedback_fraction, lh_feedback_fraction, sfc_layer_thickness
+    call check(icar_hip_lsm_configure(ctx%p, int(landsurface,c_int), int(watersurface,c_int), int(update_interval,c_int), &
+                                      real(sh_feedback_fraction,c_float), real(lh_feedback_fraction,c_float), real(sfc_layer_thickness,c_float)), "lsm_configure")
+  end subroutine
+
+  !> u_10m, v_10m and ustar of diagnostic_update (time_step.f90:143-161); ICAR_F_ROUGHNESS_Z0 uploaded
+  subroutine hip_diag_10m(ctx)
+    type(hip_ctx_t), intent(in) :: ctx
+    call check(icar_hip_diag_10m(ctx%p), "diag_10m")
+  end subroutine
+
+  !> the gated block of lsm with watersurface = kWATER_SIMPLE (lsm_driver.f90:1028-1073, water_simple.f90:83-136)
+  subroutine hip_water_simple(ctx)
+    type(hip_ctx_t), intent(in) :: ctx
+    call check(icar_hip_water_simple(ctx%p), "water_simple")
+  end subroutine
+
+  !> apply_fluxes(domain, dt) (lsm_driver.f90:361-423) on an explicit tile
+  subroutine hip_apply_fluxes(ctx, dt, its, ite, jts, jte, kts, kte)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    integer, intent(in) :: its, ite, jts, jte, kts, kte
+    call check(icar_hip_apply_fluxes(ctx%p, real(dt,c_float), int(its,c_int), int(ite,c_int), int(jts,c_int), int(jte,c_int), &
+                                     int(kts,c_int), int(kte,c_int)), "apply_fluxes")
+  end subroutine
+
+  !> lsm(domain, options, dt) (lsm_driver.f90:1005-1554) on the tile of hip_step_configure; dt = real(dt%seconds())
+  subroutine hip_lsm(ctx, dt)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    call check(icar_hip_lsm(ctx%p, real(dt,c_float)), "lsm")
+  end subroutine
+
+  !> apply_fluxes' nz (the levels below sfc_layer_thickness) for the configured tile
+  function hip_lsm_layers(ctx) result(nz)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer :: nz
+    integer(c_int) :: n
+    call check(icar_hip_lsm_layers(ctx%p, n), "lsm_layers")
+    nz = int(n)
+  end function
 
   subroutine hip_mp_reset(ctx)
     type(hip_ctx_t), intent(in) :: ctx

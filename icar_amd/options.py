@@ -11,7 +11,8 @@ class physics_type:                      # opt_types.f90:15-24
     advection: int = kADV_MPDATA
     windtype: int = 0
     boundarylayer: int = 0               # 0, kPBL_BASIC (nothing runs), kPBL_SIMPLE (icar_amd.pbl)
-    landsurface: int = 0                 # (read by pbl_var_request only, as in the reference)
+    landsurface: int = 0                 # 0, kLSM_BASIC (icar_amd.surface); also read by pbl_var_request, as in the reference
+    watersurface: int = 0                # 0, kWATER_BASIC (nothing runs), kWATER_SIMPLE (icar_amd.surface)
     radiation: int = 0                   # 0, kRA_BASIC (nothing runs), kRA_SIMPLE (icar_amd.radiation)
 
 
@@ -36,6 +37,14 @@ class mp_options_type:                   # opt_types.f90:30-46, defaults options
                       self.bv_g, self.av_i, self.Ef_si, self.Ef_rs, self.Ef_rg, self.Ef_ri, self.C_cubes,
                       self.C_sqrd, self.mu_r, self.t_adjust], np.float32)
         return p, np.array([int(self.Ef_rw_l), int(self.Ef_sw_l)], np.int32)
+
+
+@dataclass
+class lsm_options_type:                  # opt_types.f90:132-150, defaults options_obj.f90 (lsm_parameters namelist, :1812)
+    update_interval: int = 300           # seconds between recomputations of the fluxes
+    lh_feedback_fraction: float = 1.0
+    sh_feedback_fraction: float = 0.625
+    sfc_layer_thickness: float = 400.0   # m of atmosphere the fluxes are spread over
 
 
 @dataclass
@@ -94,6 +103,7 @@ class options_t:
     adv_options: adv_options_type = field(default_factory=adv_options_type)
     mp_options: mp_options_type = field(default_factory=mp_options_type)
     lt_options: lt_options_type = field(default_factory=lt_options_type)
+    lsm_options: lsm_options_type = field(default_factory=lsm_options_type)
     parameters: parameter_options_type = field(default_factory=parameter_options_type)
     vars_to_advect: dict = field(default_factory=dict)
     vars_to_allocate: dict = field(default_factory=dict)

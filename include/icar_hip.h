@@ -95,7 +95,21 @@ enum icar_hip_field {
     ICAR_F_SHORTWAVE = 49,
     ICAR_F_LONGWAVE = 50,
     ICAR_F_CLOUD_FRACTION = 51,
-    ICAR_N_FIELD_IDS = 52          /* every id an entry point takes is below this one */
+    ICAR_N_FIELD_IDS = 52,         /* the ids 0 .. 51 above (the fields and ra_simple's block); kept at this value like ICAR_N_FIELDS */
+    /* the surface-flux slot (src/physics/lsm_driver.f90 with landsurface = kLSM_BASIC, src/physics/water_simple.f90) and the 10 m
+     * diagnostics of diagnostic_update (src/main/time_step.f90:143-161), a block of its own.  REAL(4) (nx,ny) unless said otherwise */
+    ICAR_F_ROUGHNESS_Z0 = 52,      /* domain%roughness_z0%data_2d: uploaded = `associated`; rewritten over open water by water_simple */
+    ICAR_F_U_10M = 53,             /* domain%u_10m%data_2d   (0 outside ims+1:ime-1, jms+1:jme-1)       */
+    ICAR_F_V_10M = 54,             /* domain%v_10m%data_2d                                               */
+    ICAR_F_USTAR = 55,             /* domain%ustar           (0.1 outside that range, domain_obj.f90:419) */
+    ICAR_F_SST = 56,               /* domain%sst%data_2d                                                 */
+    ICAR_F_SKIN_TEMPERATURE = 57,  /* domain%skin_temperature%data_2d                                    */
+    ICAR_F_SENSIBLE_HEAT = 58,     /* domain%sensible_heat%data_2d                                       */
+    ICAR_F_LATENT_HEAT = 59,       /* domain%latent_heat%data_2d                                         */
+    ICAR_F_QSFC = 60,              /* lsm_driver.f90's module-private QSFC, readable for tests           */
+    ICAR_F_QFX = 61,               /* lsm_driver.f90's module-private QFX, readable for tests            */
+    ICAR_F_DZ_INTERFACE = 62,      /* domain%dz_interface%data_3d  (nx, nz, ny)                          */
+    ICAR_N_FIELD_SLOTS = 63        /* every id an entry point takes is below this one; sizes the library's tables */
 };
 
 enum { ICAR_ADV_UPWIND = 1, ICAR_ADV_MPDATA = 2 };   /* kADV_UPWIND / kADV_MPDATA, icar_constants.f90:341 */
@@ -267,6 +281,48 @@ int icar_hip_rad_configure(icar_hip_ctx *ctx, int radiation);
 int icar_hip_rad_calendar(icar_hip_ctx *ctx, int calendar, double year_start_seconds, double year_days, double next_year_days);
 int icar_hip_rad(icar_hip_ctx *ctx, float dt);
 
+/* ---- L1: the surface-flux slot (src/physics/lsm_driver.f90 for landsurface = kLSM_BASIC, src/physics/water_simple.f90) -----------
+ * icar_hip_lsm_configure: lsm_init (lsm_driver.f90:522-611, :991-1000) -- options%physics%landsurface / %watersurface and
+ *     options%lsm_options%update_interval (integer seconds, default 300), %sh_feedback_fraction (0.625), %lh_feedback_fraction (1.0),
+ *     %sfc_layer_thickness (400 m); resets last_model_time to its sentinel -999 (:1000) and forgets apply_fluxes' nz.
+ *     landsurface: 0 (lsm returns at once, :1014, whatever watersurface is) or 1 = kLSM_BASIC (fluxes prescribed by the host or
+ *     computed over open water, applied to the atmosphere).  2 (kLSM_SIMPLE) is refused as the reference refuses it: "Simple LSM
+ *     not settup, choose a different LSM options" (:615); 3 (kLSM_NOAH) and 4 (kLSM_NOAHMP) are refused: not built.  watersurface:
+ *     0, 1 (kWATER_BASIC: nothing runs, :1038-1050) or ICAR_WATER_SIMPLE = kWATER_SIMPLE; 3 (kWATER_LAKE) is refused: not built.
+ *     The values are looked at before the context.  QSFC = water_vapor(:,kms,:) (:568) is taken here when water_vapor is on the
+ *     device, else at the first icar_hip_water_simple.  Kept out of icar_hip_step_config so that the struct keeps its layout.
+ * icar_hip_diag_10m == time_step.f90:143-161 of diagnostic_update: u_10m, v_10m and ustar on ims+1:ime-1, jms+1:jme-1 from
+ *     ROUGHNESS_Z0, Z, TERRAIN, U_MASS, V_MASS (u_10m = (u_mass currw) lastw, the product rounded in between as it passes
+ *     through domain%ustar).  icar_hip_diagnostic_update and the step entry points call it behind the mass-point winds whenever
+ *     ROUGHNESS_Z0 has been uploaded (the reference's `associated` test); without it nothing new is issued.
+ * icar_hip_water_simple == the gated block of lsm with watersurface = kWATER_SIMPLE (lsm_driver.f90:1028-1073): windspd =
+ *     sqrt(u_10m**2 + v_10m**2), `where(wind==0) wind=1e-5` (the one visible effect of calc_exchange_coefficient on this path:
+ *     its result CHS is read by Noah alone and is NOT built), then water_simple (water_simple.f90:83-136) on 2..nx-1, 2..ny-1 of
+ *     the MEMORY rectangle where LAND_MASK == kLC_WATER: QSFC = 0.98 sat_mr(SST, SURFACE_PRESSURE), ROUGHNESS_Z0 = 8e-6 /
+ *     max(USTAR, 1e-7) (read by the next icar_hip_diag_10m), SENSIBLE_HEAT, QFX, LATENT_HEAT = QFX LH_vaporization,
+ *     SKIN_TEMPERATURE = SST, from TEMPERATURE(:,kms,:), WATER_VAPOR(:,kms,:) and z_atm = Z(:,kms,:) - TERRAIN.  Land cells keep
+ *     what the host uploaded.
+ * icar_hip_apply_fluxes == apply_fluxes(domain, dt) (lsm_driver.f90:361-423): SENSIBLE_HEAT and LATENT_HEAT into
+ *     POTENTIAL_TEMPERATURE and WATER_VAPOR of its:ite, jts:jte on the levels kts .. kts+nz with DENSITY, EXNER, DZ_INTERFACE, then
+ *     where(qv < 1e-10) qv = 1e-10 over the WHOLE array.  nz is the last level (its absolute index) at which the running sum of
+ *     maxval(dz_interface(:,k,:)) over THIS CONTEXT'S MEMORY is below sfc_layer_thickness: found once, again when DZ_INTERFACE
+ *     is uploaded or the slot reconfigured; a tiling can find another nz than one image does, in the reference and here.  The
+ *     loop runs one level past nz (with kts > kms further still); where that passes kte the reference reads out of bounds and
+ *     this call is refused before any launch ("the surface layer reaches kte").
+ * icar_hip_lsm == lsm(domain, options, dt) (:1005-1554): the gate on the library clock (:1016-1023: REAL(8), the block runs when
+ *     model_time - last_model_time >= update_interval), icar_hip_water_simple inside it when watersurface = 2, then
+ *     icar_hip_apply_fluxes on the tile of icar_hip_step_configure, every call.  icar_hip_substep / _step / _step_n call it
+ *     between rad and pbl (time_step.f90:491) when dt > 1e-3.
+ * icar_hip_lsm_layers: apply_fluxes' nz for the configured tile's kts..kte, for tests and logs. */
+enum { ICAR_LSM_BASIC = 1, ICAR_WATER_SIMPLE = 2 };
+int icar_hip_lsm_configure(icar_hip_ctx *ctx, int landsurface, int watersurface, int update_interval, float sh_feedback_fraction,
+                           float lh_feedback_fraction, float sfc_layer_thickness);
+int icar_hip_diag_10m(icar_hip_ctx *ctx);
+int icar_hip_water_simple(icar_hip_ctx *ctx);
+int icar_hip_apply_fluxes(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, int jte, int kts, int kte);
+int icar_hip_lsm(icar_hip_ctx *ctx, float dt);
+int icar_hip_lsm_layers(icar_hip_ctx *ctx, int *nz);
+
 /* ---- T2: CFL reduction for compute_dt (src/main/time_step.f90:217-330, cfl_strictness 3) -----
  * out = max over the tile of max(|u_i|,|u_i+1|)/dx + max(|v_j|,|v_j+1|)/dx + max(|w_k|,|w_k-1|)/dz_levels(k) */
 int icar_hip_max_courant(icar_hip_ctx *ctx, float dx, const float *dz_levels, float *out);
@@ -287,7 +343,8 @@ int icar_hip_max_abs_winds(icar_hip_ctx *ctx, float out[3]);
  * rho=p/(Rd T), u_mass, v_mass, w_real (uses DZDX, DZDY, JACOBIAN).  The optional column integrals ivt / iwv / iwl / iwi
  * (compute_ivt, compute_iq: src/utilities/atm_utilities.f90:35-102) are computed for every one of ICAR_F_IVT..IWI the
  * host has uploaded once (= `associated(domain%ivt%data_2d)`); iwl / iwi sum the hydrometeor fields that are on the
- * device, like the reference's `associated` tests.  The 10 m winds need roughness_z0 (LSM) and stay host-side. */
+ * device, like the reference's `associated` tests.  The 10 m winds and ustar (:143-161) likewise once ICAR_F_ROUGHNESS_Z0 has
+ * been uploaded (icar_hip_diag_10m). */
 int icar_hip_diagnostic_update(icar_hip_ctx *ctx);
 /* the same in two parts, for a host that overlaps: parts = 1: everything but w_real (what the microphysics and the advection
  * read: exner, density ...) ; 2: w_real only (:165-194; read by WSM3 and the output, not by Thompson / mp_simple / WSM6 / advect:
@@ -514,7 +571,7 @@ int icar_hip_step_n(icar_hip_ctx *ctx, int nsteps, double *dt_last);
 
 /* ---- measurement helpers --------------------------------------------------------------------- */
 /* Average duration (ms) of the launches of a named kernel group since the last reset, measured
- * with HIP events on the context's stream (bench.py roofline block). group: "advect", "mp", "pbl", "rad" ... */
+ * with HIP events on the context's stream (bench.py roofline block). group: "advect", "mp", "pbl", "rad", "diag_10m", "lsm_water", "lsm_fluxes" ... */
 int icar_hip_timing_enable(icar_hip_ctx *ctx, int on);
 /* restrict the timers to a comma-separated list of groups ("advect", "advect,mp,winds"; NULL or "" = all): every timed
  * scope costs its stream two timestamped barrier packets, ~5 us -- a dozen groups per sub-step are 10 % of a small tile's step */
