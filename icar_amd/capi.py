@@ -33,6 +33,7 @@ SYMBOLS = [
     "icar_hip_pbl_simple", "icar_hip_pbl_configure", "icar_hip_pbl", "icar_hip_pbl_nsubsteps",
     "icar_hip_ra_simple", "icar_hip_rad_configure", "icar_hip_rad_calendar", "icar_hip_rad",
     "icar_hip_lsm_configure", "icar_hip_diag_10m", "icar_hip_water_simple", "icar_hip_apply_fluxes", "icar_hip_lsm", "icar_hip_lsm_layers",
+    "icar_hip_cu_configure", "icar_hip_cu_bmj", "icar_hip_convect", "icar_hip_cu_reset", "icar_hip_cu_upload", "icar_hip_cu_download", "icar_hip_cu_tables",
 ]
 
 
@@ -114,6 +115,14 @@ def lib():
         L.icar_hip_apply_fluxes.argtypes = [vp, ctypes.c_float, ci, ci, ci, ci, ci, ci]
         L.icar_hip_lsm.argtypes = [vp, ctypes.c_float]
         L.icar_hip_lsm_layers.argtypes = [vp, ctypes.POINTER(ci)]
+        cf = ctypes.c_float
+        L.icar_hip_cu_configure.argtypes = [vp, ci, cf, cf, cf, cf, cf, cf]
+        L.icar_hip_cu_bmj.argtypes = [vp, cf, ci, ci, ci, ci]
+        L.icar_hip_convect.argtypes = [vp, cf]
+        L.icar_hip_cu_reset.argtypes = [vp]
+        L.icar_hip_cu_upload.argtypes = [vp, ci, vp]
+        L.icar_hip_cu_download.argtypes = [vp, ci, vp]
+        L.icar_hip_cu_tables.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
         _lib = L
     return _lib
 

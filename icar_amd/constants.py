@@ -21,6 +21,12 @@ kLSM_BASIC = 1
 kLSM_SIMPLE = 2
 kLSM_NOAH = 3
 kLSM_NOAHMP = 4
+kNO_STOCHASTIC = -9999           # icar_constants.f90:340-345 (convection)
+kCU_TIEDTKE = 1
+kCU_SIMPLE = 2
+kCU_KAINFR = 3
+kCU_NSAS = 4
+kCU_BMJ = 5
 kLC_LAND = 1                    # land_mask values, icar_constants.f90
 kLC_WATER = 2
 kDEFAULT_HALO_SIZE = 1          # icar_constants.f90:320

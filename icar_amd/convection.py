@@ -1,0 +1,105 @@
+"""convection driver mirror (src/physics/cu_driver.f90): cu_var_request / init_convection / convect, plus the scheme on its own.
+
+Only convection = kCU_BMJ (Betts-Miller-Janjic, src/physics/cu_bmj.f90) is built; Tiedtke and NSAS are refused by the library as not
+built, kCU_SIMPLE and kCU_KAINFR because the reference has no branch for them.  The slot's own arrays (CLDEFI, RAINCV, CUTOP, CUBOT,
+accumulated_convective_pcp, tend%th, tend%qv) have no field id: cu_get / cu_set move them by the ICAR_CU_* names below."""
+import ctypes
+import numpy as np
+from .capi import lib, check
+from .constants import kCU_BMJ, kNO_STOCHASTIC
+
+# enum icar_hip_cu_array (include/icar_hip.h)
+CU_CLDEFI, CU_ACC_CONV_PCP, CU_RAINCV, CU_CUTOP, CU_CUBOT, CU_TEND_TH, CU_TEND_QV, CU_N = range(8)
+CU_NAMES = {"cldefi": CU_CLDEFI, "accumulated_convective_pcp": CU_ACC_CONV_PCP, "raincv": CU_RAINCV, "cutop": CU_CUTOP, "cubot": CU_CUBOT,
+            "tend_th": CU_TEND_TH, "tend_qv": CU_TEND_QV}
+# BMJINIT's tables in the order of icar_hip_cu_tables, with their Fortran shapes
+CU_TABLES = (("QS0", (134,)), ("SQS", (134,)), ("PTBL", (76, 134)), ("THE0", (76,)), ("STHE", (76,)), ("TTBL", (134, 76)),
+             ("THE0Q", (152,)), ("STHEQ", (152,)), ("TTBLQ", (440, 152)))
+
+
+def cu_var_request(options):
+    """cu_driver.f90:75-89: the kVARS the BMJ branch allocates, advects and writes to restart files"""
+    if options.physics.convection != kCU_BMJ:
+        return
+    options.alloc_vars(["water_vapor", "potential_temperature", "temperature", "cloud_water", "cloud_ice", "precipitation",
+                        "convective_precipitation", "exner", "dz_interface", "density", "pressure_interface", "pressure",
+                        "sensible_heat", "latent_heat", "u", "v", "w", "land_mask", "tend_qv", "tend_th", "tend_qc", "tend_qi", "tend_qs",
+                        "tend_qr", "tend_u", "tend_v", "kpbl"])
+    options.advect_vars(["potential_temperature", "water_vapor"])
+    options.restart_vars(["water_vapor", "potential_temperature", "temperature", "cloud_water", "cloud_ice", "precipitation",
+                          "convective_precipitation", "sensible_heat", "latent_heat", "u", "v", "pressure", "kpbl"])
+
+
+def cu_configure(domain, convection, stochastic_cu=float(kNO_STOCHASTIC), tendency_fraction=1.0, tend_qv_fraction=-1.0, tend_qc_fraction=-1.0,
+                 tend_th_fraction=-1.0, tend_qi_fraction=-1.0):
+    """icar_hip_cu_configure: options%physics%convection and options%cu_options; with kCU_BMJ the slot's arrays, BMJINIT's tables and
+    the column workspace are made on the first call"""
+    check(lib().icar_hip_cu_configure(domain.ctx, int(convection), float(stochastic_cu), float(tendency_fraction), float(tend_qv_fraction),
+                                      float(tend_qc_fraction), float(tend_th_fraction), float(tend_qi_fraction)), "icar_hip_cu_configure")
+    inherit = lambda f: float(tendency_fraction) if f < 0 else float(f)
+    domain._cu_key = (0,) if int(convection) == 0 else (int(convection), float(stochastic_cu), float(tendency_fraction), inherit(tend_qv_fraction),
+                                                       inherit(tend_qc_fraction), inherit(tend_th_fraction), inherit(tend_qi_fraction))
+
+
+def init_convection(domain, options):
+    """init_convection (cu_driver.f90:97-253): the options to the library; CLDEFI = AVGEFI, the tables of BMJINIT"""
+    o = options.cu_options
+    cu_configure(domain, options.physics.convection, o.stochastic_cu, o.tendency_fraction, o.tend_qv_fraction, o.tend_qc_fraction,
+                 o.tend_th_fraction, o.tend_qi_fraction)
+
+
+def convect(domain, options, dt):
+    """convect(domain, options, dt) (cu_driver.f90:255-514) on the tile its..kte of the domain's grid; dt a REAL(4) like real(dt%seconds())"""
+    if options.physics.convection == 0:
+        return
+    domain.configure(options)
+    check(lib().icar_hip_convect(domain.ctx, float(dt)), "icar_hip_convect")
+
+
+def cu_bmj(domain, dt, its, ite, jts, jte):
+    """the call of BMJDRV alone (cu_driver.f90:434-465) on a range of columns, the levels those of the configured step (else kms..kme)"""
+    check(lib().icar_hip_cu_bmj(domain.ctx, float(dt), int(its), int(ite), int(jts), int(jte)), "icar_hip_cu_bmj")
+
+
+def cu_reset(domain):
+    """CLDEFI = AVGEFI, accumulated_convective_pcp = 0"""
+    check(lib().icar_hip_cu_reset(domain.ctx), "icar_hip_cu_reset")
+
+
+def _shape(domain, which):
+    return (domain.ny, domain.nz, domain.nx) if which in (CU_TEND_TH, CU_TEND_QV) else (domain.ny, domain.nx)
+
+
+def cu_set(domain, name, array):
+    which = CU_NAMES[name] if isinstance(name, str) else int(name)
+    a = np.ascontiguousarray(array, np.float32)
+    if a.shape != _shape(domain, which):
+        raise ValueError(f"{name}: shape {a.shape} != {_shape(domain, which)}")
+    check(lib().icar_hip_cu_upload(domain.ctx, which, a.ctypes.data_as(ctypes.c_void_p)), f"icar_hip_cu_upload {name}")
+
+
+def cu_get(domain, name):
+    which = CU_NAMES[name] if isinstance(name, str) else int(name)
+    a = np.empty(_shape(domain, which), np.float32)
+    check(lib().icar_hip_cu_download(domain.ctx, which, a.ctypes.data_as(ctypes.c_void_p)), f"icar_hip_cu_download {name}")
+    return a
+
+
+def cu_tables(domain):
+    """{name: array (C order: the Fortran shape reversed)} of BMJINIT's tables as they sit on the device"""
+    n = ctypes.c_size_t()
+    check(lib().icar_hip_cu_tables(domain.ctx, None, 0, ctypes.byref(n)), "icar_hip_cu_tables")
+    block = np.empty(n.value, np.float32)
+    check(lib().icar_hip_cu_tables(domain.ctx, block.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)), "icar_hip_cu_tables")
+    out, o = {}, 0
+    for name, shape in CU_TABLES:
+        cnt = int(np.prod(shape))
+        out[name] = block[o:o + cnt].reshape(shape[::-1]).copy()
+        o += cnt
+    return out
+
+
+def cu_finalize(options, domain=None):
+    """the slot is switched off (its arrays stay until the context goes)"""
+    if domain is not None:
+        cu_configure(domain, 0)

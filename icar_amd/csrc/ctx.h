@@ -26,6 +26,7 @@ struct LinWinds;         // linear_winds.hip
 struct Wsm3State;        // mp_wsm3.hip
 struct Wsm6State;        // mp_wsm6.hip
 struct IcarComm;         // comm.hip
+struct CuState;          // cu_bmj.hip
 
 // state of the step driver (timestep.hip): the options / grid members the sub-step loop reads, the model clock, and what
 // mp_driver.f90 keeps in SAVE variables (last_model_time)
@@ -52,6 +53,9 @@ struct IcarStepState {
     int landsurface = 0, watersurface = 0, lsm_update_interval = 300;
     float sh_feedback_fraction = 0.625f, lh_feedback_fraction = 1.0f, sfc_layer_thickness = 400.0f;
     double lsm_last_model_time = -999.0;
+    // icar_hip_cu_configure: options%physics%convection (0 or ICAR_CU_BMJ) and options%cu_options with the fractions already inherited
+    int convection = 0;
+    float cu_tendency_fraction = 1.0f, cu_tend_qv_fraction = 1.0f, cu_tend_qc_fraction = 1.0f, cu_tend_th_fraction = 1.0f, cu_tend_qi_fraction = 1.0f;
 };
 
 // component indices of the per-cell coefficients in icar_hip_ctx::mpc (k_mpdata_coef in mpdata.hip says what they hold): the first
@@ -104,6 +108,7 @@ struct icar_hip_ctx {
     int sfc_nz = 0, sfc_nz_kts = 0, sfc_nz_kte = 0;
     float sfc_nz_thick = 0.0f;
     unsigned *sfc_levelmax = nullptr;
+    CuState *cu = nullptr;               // cu_bmj.hip: the convection slot's arrays, BMJINIT's tables and the column workspace
     // reductions / flags
     float *d_red = nullptr;              // small device scratch for reductions
     std::vector<float> dzl_host;         // dz_levels last uploaded behind d_red (compute_dt re-sends them only when they change)
@@ -163,6 +168,14 @@ int icar_sfc_layers(icar_hip_ctx *c, int kts, int kte, int *nz_out);
 int icar_sfc_apply_fluxes_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);
 int icar_lsm_run(icar_hip_ctx *c, float dt);                                // lsm(domain, options, dt): the gate, water_simple, apply_fluxes on the step's tile
 int icar_lsm_init_device(icar_hip_ctx *c);
+// cu_bmj.hip
+void icar_cu_free(icar_hip_ctx *c);
+int icar_cu_init_device(icar_hip_ctx *c);                                   // init_convection for kCU_BMJ: arrays, tables, workspace
+int icar_cu_bmj_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);
+int icar_convect_run(icar_hip_ctx *c, float dt);                            // convect(domain, options, dt) on the step's tile
+int icar_cu_copy(icar_hip_ctx *c, int which, void *host, bool to_device);
+int icar_cu_reset_run(icar_hip_ctx *c);
+int icar_cu_tables_copy(icar_hip_ctx *c, float *out, size_t capacity, size_t *n_out);
 // timestep.hip
 int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset);      // halo / subset < 0: argument not present
 int icar_update_dt(icar_hip_ctx *c, double *seconds);

@@ -12,6 +12,8 @@
 //   [lsm, when icar_hip_lsm_configure switched it on: it reads the 10 m winds, which follow the mass-point winds -- the whole of
 //    part 1 runs in front of it; time_step.f90:491]
 //   [pbl, when icar_hip_pbl_configure switched it on: it reads u_mass / v_mass, so the whole of part 1 runs in front of it]
+//   [convect, when icar_hip_cu_configure switched it on: BMJ reads temperature, density and pressure_interface as diagnostic_update
+//    left them -- the whole of part 1 runs in front of it; time_step.f90:509]
 //   mp(subset=1) interior                                 mp(halo=1) strips -> halo_send (pack + RCCL)   time_step.f90:512-526
 //   |                                                     interface values, mass-point winds (k_diag_face)
 //   |                                                     setup_module_winds (+ MPDATA coefficients) of the advect() that follows,
@@ -208,6 +210,7 @@ bool icar_substep_can_open_early(icar_hip_ctx *c)
     if (c->step.boundarylayer == ICAR_PBL_SIMPLE) return false;                   // pbl(domain, options, dt) opens the sub-step and takes dt
     if (c->step.radiation == ICAR_RA_SIMPLE) return false;                        // rad(domain, options, dt) likewise
     if (c->step.landsurface != 0) return false;                                   // lsm(domain, options, dt) likewise
+    if (c->step.convection != 0) return false;                                    // convect(domain, options, dt) likewise
     return g.microphysics != 0 && g.halo_size == 1 && g.mp_update_interval == 0.0f && c->step.mp_last_model_time != -999.0
         && g.prefetch_dt && (g.cfl_strictness == 3 || g.cfl_strictness == 4) && icar_cfl_prefetch_waiting(c) && !c->on_aux;
 }
@@ -218,7 +221,8 @@ bool icar_substep_can_open_early(icar_hip_ctx *c)
 // unless something on the device reads them before the next diagnostic_update rewrites them.  Who reads what:
 //   exner                 every microphysics scheme, ra_simple                        -> always written
 //   density               mp_simple, WSM6, WSM3, pbl_simple, the Courant winds with advect_density
-//   temperature           the interface kernel only (k_diag_face)
+//   temperature           the interface kernel (k_diag_face), lsm, BMJ
+//   pressure_interface    BMJ
 //   u_mass, v_mass, interface values   pbl_simple, the column integrals
 //   w_real                WSM3
 // Returns what the cell kernel of such a sub-step stores (ICAR_DIAG_EXNER / ICAR_DIAG_EXNER_RHO; its face kernel and w_real are
@@ -230,6 +234,7 @@ static int lazy_diag_part(icar_hip_ctx *c, bool last)
     if (last || !g.diagnostics) return 0;
     if (c->step.boundarylayer == ICAR_PBL_SIMPLE || c->step.radiation == ICAR_RA_SIMPLE || g.advect_density || icar_diag_columns_on(c)) return 0;
     if (c->step.landsurface != 0) return 0;                                       // lsm reads temperature, density, the 10 m winds and ustar
+    if (c->step.convection != 0) return 0;                                        // BMJ reads temperature, density and pressure_interface
     if (g.microphysics == kMP_THOMPSON) return ICAR_DIAG_EXNER;                                   // reads exner, p, th, dz
     if (g.microphysics == kMP_SB04 || g.microphysics == kMP_WSM6) return ICAR_DIAG_EXNER_RHO;     // ... and density
     return 0;                                                                                     // WSM3 (w_real, density), no microphysics
@@ -303,6 +308,7 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
     const bool adv = (g.advection == ICAR_ADV_UPWIND || g.advection == ICAR_ADV_MPDATA);
     const bool stepping = dt > 1e-3;                                              // :483
     const bool pbl = c->step.boundarylayer == ICAR_PBL_SIMPLE, rad = c->step.radiation == ICAR_RA_SIMPLE, lsm = c->step.landsurface != 0;
+    const bool cu = c->step.convection != 0;
     bool wreal_later = false, face_later = false, wreal_done = false;
     const bool early = c->step.early_open;
     c->step.early_open = false;
@@ -330,7 +336,8 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
             // (simple_pbl reads u_mass and v_mass, ra_simple rewrites the potential_temperature the interface values are made of:
             // nothing of part 1 can wait)
             // (lsm reads u_10m, v_10m and ustar, which are made behind the mass-point winds)
-            face_later = stepping && g.microphysics != 0 && !pbl && !rad && !lsm;
+            // (BMJ reads pressure_interface, which the interface kernel writes)
+            face_later = stepping && g.microphysics != 0 && !pbl && !rad && !lsm && !cu;
             if (icar_diagnostic_update_run(c, face_later ? ICAR_DIAG_CELL : 1)) return 1;
             if (stepping) wreal_later = true;                                     // beside the advection, below
             else if (icar_diagnostic_update_run(c, 2)) return 1;
@@ -341,6 +348,7 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
     if (rad && icar_rad_run(c, dtf)) return 1;                                    // :488 rad(domain, options, real(dt%seconds()))
     if (lsm && icar_lsm_run(c, dtf)) return 1;                                    // :491 lsm(domain, options, real(dt%seconds()))
     if (pbl && icar_pbl_run(c, dtf)) return 1;                                    // :494 pbl(domain, options, real(dt%seconds()))
+    if (cu && icar_convect_run(c, dtf)) return 1;                                 // :509 convect(domain, options, real(dt%seconds()))
 
     // :512-526  mp(halo=1) -> halo_send -> mp(subset=1) -> halo_retrieve
     if (early) {
@@ -601,6 +609,73 @@ int icar_hip_lsm_layers(icar_hip_ctx *c, int *nz)
     if (!cfg_ok(c, "lsm_layers")) return 1;
     HIPCHK(hipSetDevice(c->device));
     return icar_sfc_layers(c, c->step.cfg.kts, c->step.cfg.kte, nz);
+}
+
+int icar_hip_cu_configure(icar_hip_ctx *c, int convection, float stochastic_cu, float tendency_fraction, float tend_qv_fraction,
+                          float tend_qc_fraction, float tend_th_fraction, float tend_qi_fraction)
+{
+    // the values are looked at first: a host learns what is not built without a device
+    if (convection == 1) { icar_set_error("cu_configure: convection = 1 (kCU_TIEDTKE) is not built; 0 or 5 (kCU_BMJ)"); return 1; }
+    if (convection == 4) { icar_set_error("cu_configure: convection = 4 (kCU_NSAS) is not built; 0 or 5 (kCU_BMJ)"); return 1; }
+    if (convection == 2) { icar_set_error("cu_configure: convection = 2 (kCU_SIMPLE): cu_driver.f90 has no branch for it and cu_simple.f90 is not among the reference's objects; 0 or 5 (kCU_BMJ)"); return 1; }
+    if (convection == 3) { icar_set_error("cu_configure: convection = 3 (kCU_KAINFR): its branch in cu_driver.f90 is commented out and cu_kf.f90 is not among the reference's objects; 0 or 5 (kCU_BMJ)"); return 1; }
+    if (convection != 0 && convection != ICAR_CU_BMJ) { icar_set_error("cu_configure: convection is 0 or 5 (kCU_BMJ)"); return 1; }
+    if (stochastic_cu != ICAR_CU_NO_STOCHASTIC) {
+        icar_set_error("cu_configure: stochastic_cu /= kNO_STOCHASTIC (-9999) perturbs W0AVG with random_number (cu_driver.f90:287-295): not built (and BMJ never reads W0AVG)");
+        return 1;
+    }
+    if (!(tendency_fraction == tendency_fraction)) { icar_set_error("cu_configure: tendency_fraction is NaN"); return 1; }
+    if (!c) { icar_set_error("cu_configure: null ctx"); return 1; }
+    IcarStepState &s = c->step;
+    s.cu_tendency_fraction = tendency_fraction;
+    // options_obj.f90:1646-1649: a fraction that was not set inherits the global one
+    s.cu_tend_qv_fraction = tend_qv_fraction < 0 ? tendency_fraction : tend_qv_fraction;
+    s.cu_tend_qc_fraction = tend_qc_fraction < 0 ? tendency_fraction : tend_qc_fraction;
+    s.cu_tend_th_fraction = tend_th_fraction < 0 ? tendency_fraction : tend_th_fraction;
+    s.cu_tend_qi_fraction = tend_qi_fraction < 0 ? tendency_fraction : tend_qi_fraction;
+    s.convection = convection;
+    if (convection == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    return icar_cu_init_device(c);
+}
+
+int icar_hip_cu_bmj(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte)
+{
+    if (icar_enter(c, "cu_bmj")) return 1;
+    const bool cfg = c->step.configured;
+    return icar_cu_bmj_run(c, dt, its, ite, jts, jte, cfg ? c->step.cfg.kts : c->kms, cfg ? c->step.cfg.kte : c->kme);
+}
+
+int icar_hip_convect(icar_hip_ctx *c, float dt)
+{
+    if (!c) { icar_set_error("convect: null argument"); return 1; }
+    if (!cfg_ok(c, "convect")) return 1;
+    HIPCHK(hipSetDevice(c->device));
+    return icar_convect_run(c, dt);
+}
+
+int icar_hip_cu_reset(icar_hip_ctx *c)
+{
+    if (icar_enter(c, "cu_reset")) return 1;
+    return icar_cu_reset_run(c);
+}
+
+int icar_hip_cu_upload(icar_hip_ctx *c, int which, const void *host)
+{
+    if (icar_enter(c, "cu_upload", host != nullptr)) return 1;
+    return icar_cu_copy(c, which, const_cast<void *>(host), true);
+}
+
+int icar_hip_cu_download(icar_hip_ctx *c, int which, void *host)
+{
+    if (icar_enter(c, "cu_download", host != nullptr)) return 1;
+    return icar_cu_copy(c, which, host, false);
+}
+
+int icar_hip_cu_tables(icar_hip_ctx *c, float *out, size_t capacity, size_t *count)
+{
+    if (icar_enter(c, "cu_tables", out || count)) return 1;
+    return icar_cu_tables_copy(c, out, capacity, count);
 }
 
 int icar_hip_mp(icar_hip_ctx *c, double dt, int halo, int subset)

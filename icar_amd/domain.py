@@ -33,6 +33,7 @@ class domain_t:
         self._pbl_key = 0                # options%physics%boundarylayer as last handed to icar_hip_pbl_configure
         self._rad_key = 0                # options%physics%radiation as last handed to icar_hip_rad_configure
         self._lsm_key = (0, 0)           # options%physics%landsurface / %watersurface and lsm_options as last handed to icar_hip_lsm_configure
+        self._cu_key = (0,)              # options%physics%convection and options%cu_options as last handed to icar_hip_cu_configure
         self._forced, self._diagnostics, self._prefetch_dt = (), True, True
         if comm is not None:
             comm.attach(self)            # icar_hip_comm_init[_host]: collective over the images of the communicator
@@ -54,7 +55,7 @@ class domain_t:
         check(lib().icar_hip_model_time_set(self.ctx, float(seconds)), "icar_hip_model_time_set")
 
     def configure(self, options, forced=None, diagnostics=None, prefetch_dt=None, advection=None, boundarylayer=None, radiation=None,
-                  landsurface=None, watersurface=None):
+                  landsurface=None, watersurface=None, convection=None):
         """icar_hip_step_configure: hand the library the members of options_t / grid_t that step(), update_dt(), mp() and
         advect() read (time_step.f90:440-551).  Cheap when nothing changed.  forced = [(member, force_boundaries), ...] (the
         variables apply_forcing updates), diagnostics (diagnostic_update at the top of a sub-step) and prefetch_dt stay as last
@@ -63,7 +64,9 @@ class domain_t:
         between diagnostic_update and the microphysics of every sub-step), radiation=0 options%physics%radiation
         (icar_hip_rad_configure: rad() then runs in front of pbl(); the calendar anchor is icar_amd.radiation.rad_calendar's),
         landsurface=0 / watersurface=0 options%physics%landsurface / %watersurface (icar_hip_lsm_configure with options%lsm_options:
-        lsm() then runs between rad() and pbl(); handed over only when they change, since that resets lsm's update gate)."""
+        lsm() then runs between rad() and pbl(); handed over only when they change, since that resets lsm's update gate),
+        convection=0 options%physics%convection (icar_hip_cu_configure with options%cu_options: convect() then runs between pbl() and
+        the microphysics; CLDEFI and the convective accumulator live on, icar_amd.convection.cu_reset starts them again)."""
         p, g = options.parameters, self.grid
         bl = int(options.physics.boundarylayer if boundarylayer is None else boundarylayer)
         if bl != self._pbl_key:
@@ -81,6 +84,13 @@ class domain_t:
             from .surface import lsm_configure
             if ls == 0 or lo is None: lsm_configure(self, ls, ws)
             else: lsm_configure(self, *lkey)
+        cu = int(getattr(options.physics, "convection", 0) if convection is None else convection)
+        co = getattr(options, "cu_options", None)
+        ckey = (0,) if cu == 0 or co is None else (cu, float(co.stochastic_cu), float(co.tendency_fraction)) + tuple(float(f) for f in co.resolved())
+        if cu != 0 and co is None: ckey = (cu, -9999.0, 1.0, 1.0, 1.0, 1.0, 1.0)
+        if ckey != self._cu_key:
+            from .convection import cu_configure
+            cu_configure(self, *ckey)
         adv = options.physics.advection if advection is None else advection
         adv_ids = tuple(KVARS[n][0] for n in ADVECTION_ORDER if options.vars_to_advect.get(n, 0) > 0)
         if forced is not None: self._forced = tuple((self.fid(n), int(bool(b))) for n, b in forced)

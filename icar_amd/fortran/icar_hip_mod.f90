@@ -23,6 +23,8 @@ module icar_hip
             hip_halo_send, hip_halo_retrieve, hip_co_min, hip_comm_ranks, hip_halo_selfcheck, hip_update_winds, hip_exchange_uv, hip_mpdata_exact, &
             hip_pbl_configure, hip_pbl, hip_pbl_simple, ICAR_PBL_SIMPLE, hip_rad_configure, hip_rad_calendar, hip_rad, hip_ra_simple, ICAR_RA_SIMPLE, &
             hip_lsm_configure, hip_diag_10m, hip_water_simple, hip_apply_fluxes, hip_lsm, hip_lsm_layers, ICAR_LSM_BASIC, ICAR_WATER_SIMPLE, &
+            hip_cu_configure, hip_cu_bmj, hip_convect, hip_cu_reset, hip_cu_upload, hip_cu_download, ICAR_CU_BMJ, ICAR_CU_NO_STOCHASTIC, &
+            ICAR_CU_CLDEFI, ICAR_CU_ACC_CONV_PCP, ICAR_CU_RAINCV, ICAR_CU_CUTOP, ICAR_CU_CUBOT, ICAR_CU_TEND_TH, ICAR_CU_TEND_QV, ICAR_CU_N, &
             ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_SELF, ICAR_N_ADVECTABLE
   public :: ICAR_F_WATER_VAPOR, ICAR_F_CLOUD_WATER, ICAR_F_RAIN, ICAR_F_SNOW, ICAR_F_POTENTIAL_TEMPERATURE, &
             ICAR_F_CLOUD_ICE, ICAR_F_GRAUPEL, ICAR_F_ICE_NUMBER, ICAR_F_RAIN_NUMBER, ICAR_F_U, ICAR_F_V, ICAR_F_W, &
@@ -52,6 +54,11 @@ module icar_hip
   integer(c_int), parameter :: ICAR_PBL_SIMPLE = 2      ! kPBL_SIMPLE, icar_constants.f90:355
   integer(c_int), parameter :: ICAR_LSM_BASIC = 1, ICAR_WATER_SIMPLE = 2     ! kLSM_BASIC, kWATER_SIMPLE, icar_constants.f90:358-365
   integer(c_int), parameter :: ICAR_RA_SIMPLE = 2       ! kRA_SIMPLE, icar_constants.f90
+  integer(c_int), parameter :: ICAR_CU_BMJ = 5          ! kCU_BMJ, icar_constants.f90:345
+  real(c_float), parameter :: ICAR_CU_NO_STOCHASTIC = -9999.0   ! kNO_STOCHASTIC, icar_constants.f90:340
+  ! enum icar_hip_cu_array (include/icar_hip.h): the convection slot's own arrays, REAL(4) (nx,ny) but for the two tendencies (nx,nz,ny)
+  integer(c_int), parameter :: ICAR_CU_CLDEFI=0, ICAR_CU_ACC_CONV_PCP=1, ICAR_CU_RAINCV=2, ICAR_CU_CUTOP=3, ICAR_CU_CUBOT=4, &
+       ICAR_CU_TEND_TH=5, ICAR_CU_TEND_QV=6, ICAR_CU_N=7
 
   !> struct icar_hip_step_config == the members of options_t / grid_t the sub-step loop reads (time_step.f90:440-551)
   type, bind(C) :: hip_step_config_t
@@ -184,6 +191,26 @@ module icar_hip
      end function
      integer(c_int) function icar_hip_lsm_layers(ctx, nz) bind(C, name="icar_hip_lsm_layers")
        import; type(c_ptr), value :: ctx; integer(c_int) :: nz
+     end function
+     integer(c_int) function icar_hip_cu_configure(ctx, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, &
+                                                   tend_th_fraction, tend_qi_fraction) bind(C, name="icar_hip_cu_configure")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: convection
+       real(c_float), value :: stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction
+     end function
+     integer(c_int) function icar_hip_cu_bmj(ctx, dt, its, ite, jts, jte) bind(C, name="icar_hip_cu_bmj")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt; integer(c_int), value :: its, ite, jts, jte
+     end function
+     integer(c_int) function icar_hip_convect(ctx, dt) bind(C, name="icar_hip_convect")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt
+     end function
+     integer(c_int) function icar_hip_cu_reset(ctx) bind(C, name="icar_hip_cu_reset")
+       import; type(c_ptr), value :: ctx
+     end function
+     integer(c_int) function icar_hip_cu_upload(ctx, which, host) bind(C, name="icar_hip_cu_upload")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
+     end function
+     integer(c_int) function icar_hip_cu_download(ctx, which, host) bind(C, name="icar_hip_cu_download")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
      end function
      integer(c_int) function icar_hip_wsm6_init(ctx) bind(C, name="icar_hip_wsm6_init")
        import; type(c_ptr), value :: ctx
@@ -511,6 +538,53 @@ contains
     call check(icar_hip_lsm_layers(ctx%p, n), "lsm_layers")
     nz = int(n)
   end function
+
+  !> init_convection (cu_driver.f90:97-253): options%physics%convection (0 or ICAR_CU_BMJ; Tiedtke and NSAS are not built, 2 and 3 have no
+  !! branch in the reference) and options%cu_options (stochastic_cu must be kNO_STOCHASTIC; a negative fraction inherits tendency_fraction)
+  subroutine hip_cu_configure(ctx, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer, intent(in) :: convection
+    real, intent(in) :: stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction
+    call check(icar_hip_cu_configure(ctx%p, int(convection,c_int), real(stochastic_cu,c_float), real(tendency_fraction,c_float), &
+                                     real(tend_qv_fraction,c_float), real(tend_qc_fraction,c_float), real(tend_th_fraction,c_float), &
+                                     real(tend_qi_fraction,c_float)), "cu_configure")
+  end subroutine
+
+  !> the call of BMJDRV alone (cu_driver.f90:434-465) on a range of columns
+  subroutine hip_cu_bmj(ctx, dt, its, ite, jts, jte)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    integer, intent(in) :: its, ite, jts, jte
+    call check(icar_hip_cu_bmj(ctx%p, real(dt,c_float), int(its,c_int), int(ite,c_int), int(jts,c_int), int(jte,c_int)), "cu_bmj")
+  end subroutine
+
+  !> convect(domain, options, dt) (cu_driver.f90:255-514) on the tile of hip_step_configure; dt = real(dt%seconds())
+  subroutine hip_convect(ctx, dt)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    call check(icar_hip_convect(ctx%p, real(dt,c_float)), "convect")
+  end subroutine
+
+  !> CLDEFI = AVGEFI, accumulated_convective_pcp = 0
+  subroutine hip_cu_reset(ctx)
+    type(hip_ctx_t), intent(in) :: ctx
+    call check(icar_hip_cu_reset(ctx%p), "cu_reset")
+  end subroutine
+
+  !> the slot's own arrays by ICAR_CU_*: a contiguous REAL(4) array of (nx,ny), or (nx,nz,ny) for the two tendencies
+  subroutine hip_cu_upload(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(in), target, contiguous :: a(..)
+    call check(icar_hip_cu_upload(ctx%p, which, c_loc(a)), "cu_upload")
+  end subroutine
+
+  subroutine hip_cu_download(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(inout), target, contiguous :: a(..)
+    call check(icar_hip_cu_download(ctx%p, which, c_loc(a)), "cu_download")
+  end subroutine
 
   subroutine hip_mp_reset(ctx)
     type(hip_ctx_t), intent(in) :: ctx

@@ -14,6 +14,7 @@ class physics_type:                      # opt_types.f90:15-24
     landsurface: int = 0                 # 0, kLSM_BASIC (icar_amd.surface); also read by pbl_var_request, as in the reference
     watersurface: int = 0                # 0, kWATER_BASIC (nothing runs), kWATER_SIMPLE (icar_amd.surface)
     radiation: int = 0                   # 0, kRA_BASIC (nothing runs), kRA_SIMPLE (icar_amd.radiation)
+    convection: int = 0                  # 0, kCU_BMJ (icar_amd.convection)
 
 
 @dataclass
@@ -45,6 +46,20 @@ class lsm_options_type:                  # opt_types.f90:132-150, defaults optio
     lh_feedback_fraction: float = 1.0
     sh_feedback_fraction: float = 0.625
     sfc_layer_thickness: float = 400.0   # m of atmosphere the fluxes are spread over
+
+
+@dataclass
+class cu_options_type:                   # opt_types.f90 cu_options_type, defaults options_obj.f90:1630-1649 (cu_parameters namelist)
+    stochastic_cu: float = -9999.0       # kNO_STOCHASTIC
+    tendency_fraction: float = 1.0
+    tend_qv_fraction: float = -1.0       # negative: inherits tendency_fraction (:1646-1649)
+    tend_qc_fraction: float = -1.0
+    tend_th_fraction: float = -1.0
+    tend_qi_fraction: float = -1.0
+
+    def resolved(self):
+        """(tend_qv, tend_qc, tend_th, tend_qi)_fraction as cu_parameters_namelist stores them"""
+        return tuple(self.tendency_fraction if f < 0 else f for f in (self.tend_qv_fraction, self.tend_qc_fraction, self.tend_th_fraction, self.tend_qi_fraction))
 
 
 @dataclass
@@ -104,6 +119,7 @@ class options_t:
     mp_options: mp_options_type = field(default_factory=mp_options_type)
     lt_options: lt_options_type = field(default_factory=lt_options_type)
     lsm_options: lsm_options_type = field(default_factory=lsm_options_type)
+    cu_options: cu_options_type = field(default_factory=cu_options_type)
     parameters: parameter_options_type = field(default_factory=parameter_options_type)
     vars_to_advect: dict = field(default_factory=dict)
     vars_to_allocate: dict = field(default_factory=dict)

@@ -34,11 +34,12 @@ def update_dt(domain, options):
 def mp_and_halo(domain, options, dt):
     """time_step.f90:512-526 alone: mp(halo=1) -> halo_send -> mp(subset=1) -> halo_retrieve, the strips, the pack kernels and
     the exchange on the context's main stream, the interior launch beside them on its second stream -- icar_hip_substep with the
-    rest of the sub-step (diagnostic_update, rad, lsm, pbl, advect, apply_forcing) switched off.  (Switching lsm off and on again
+    rest of the sub-step (diagnostic_update, rad, lsm, pbl, convect, advect, apply_forcing) switched off.  (Switching lsm off and on again
     hands its options to the library anew, which resets lsm's update gate as lsm_init does: a host that carries the gate issues the
     block through mp / halo_send / halo_retrieve instead.)"""
     keep = (domain._forced, domain._diagnostics, domain._prefetch_dt)
-    domain.configure(options, forced=(), diagnostics=False, prefetch_dt=False, advection=0, boundarylayer=0, radiation=0, landsurface=0, watersurface=0)
+    domain.configure(options, forced=(), diagnostics=False, prefetch_dt=False, advection=0, boundarylayer=0, radiation=0, landsurface=0, watersurface=0,
+                     convection=0)
     try:
         check(lib().icar_hip_substep(domain.ctx, float(dt), 0), "icar_hip_substep")
     finally:
@@ -46,7 +47,7 @@ def mp_and_halo(domain, options, dt):
 
 
 def substep(domain, options, dt, forced=None, diagnostics=True, enforce=False, prefetch_dt=True):
-    """One pass of time_step.f90:474-539: diagnostic_update -> [rad, options%physics%radiation = kRA_SIMPLE] -> [lsm, options%physics%landsurface = kLSM_BASIC] -> [pbl, options%physics%boundarylayer = kPBL_SIMPLE] -> mp(halo=1) -> halo_send -> mp(subset=1) -> halo_retrieve ->
+    """One pass of time_step.f90:474-539: diagnostic_update -> [rad, options%physics%radiation = kRA_SIMPLE] -> [lsm, options%physics%landsurface = kLSM_BASIC] -> [pbl, options%physics%boundarylayer = kPBL_SIMPLE] -> [convect, options%physics%convection = kCU_BMJ] -> mp(halo=1) -> halo_send -> mp(subset=1) -> halo_retrieve ->
     advect -> apply_forcing (-> enforce_limits), issued by ONE library call (icar_hip_substep) with the streaming kernels that do
     not depend on the two heavy ones beside them (icar_amd/csrc/timestep.hip has the table).  Same launches, same operands,
     same results as the plain sequence.  forced = [(member, force_boundaries), ...] with uploaded dqdt (domain.set_dqdt)."""
@@ -55,11 +56,12 @@ def substep(domain, options, dt, forced=None, diagnostics=True, enforce=False, p
 
 
 def step(domain, end_time, options, forced=None, diagnostics=True):
-    """time_step.f90:440-551 (cu is not built; rad runs with options%physics%radiation = kRA_SIMPLE, icar_amd.radiation, lsm with
+    """time_step.f90:440-551 (rad runs with options%physics%radiation = kRA_SIMPLE, icar_amd.radiation, lsm with
     options%physics%landsurface = kLSM_BASIC and watersurface 0, 1 or kWATER_SIMPLE, icar_amd.surface, pbl with
-    options%physics%boundarylayer = kPBL_SIMPLE, icar_amd.pbl):
+    options%physics%boundarylayer = kPBL_SIMPLE, icar_amd.pbl, convect with options%physics%convection = kCU_BMJ,
+    icar_amd.convection):
     the operator-split loop
-         update_dt -> diagnostic_update -> [rad] -> [lsm] -> [pbl] -> mp(halo=1) -> halo_send -> mp(subset=1) -> halo_retrieve
+         update_dt -> diagnostic_update -> [rad] -> [lsm] -> [pbl] -> [convect] -> mp(halo=1) -> halo_send -> mp(subset=1) -> halo_retrieve
          -> advect -> apply_forcing -> enforce_limits (last two sub-steps)
     until the model clock reaches end_time, in one library call (icar_hip_step).  Returns the number of sub-steps taken."""
     domain.configure(options, forced=forced or (), diagnostics=diagnostics, prefetch_dt=True)

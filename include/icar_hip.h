@@ -323,6 +323,61 @@ int icar_hip_apply_fluxes(icar_hip_ctx *ctx, float dt, int its, int ite, int jts
 int icar_hip_lsm(icar_hip_ctx *ctx, float dt);
 int icar_hip_lsm_layers(icar_hip_ctx *ctx, int *nz);
 
+/* ---- C1: the convection slot (src/physics/cu_driver.f90 with convection = kCU_BMJ, src/physics/cu_bmj.f90) ---------------------------
+ * icar_hip_cu_configure: init_convection (cu_driver.f90:97-253) -- options%physics%convection and options%cu_options.
+ *     convection: 0 (convect returns at once, :264) or ICAR_CU_BMJ = kCU_BMJ (icar_constants.f90:345).  1 (kCU_TIEDTKE) and 4 (kCU_NSAS)
+ *     are refused: not built.  2 (kCU_SIMPLE) is refused: cu_driver.f90 has no branch for it and cu_simple.f90 is not among the
+ *     reference's objects; 3 (kCU_KAINFR) likewise: its branch in cu_driver.f90 is commented out and cu_kf.f90 is not built.
+ *     stochastic_cu: ICAR_CU_NO_STOCHASTIC = kNO_STOCHASTIC (-9999); anything else draws from random_number in the reference
+ *     (:287-295) and is refused.  tendency_fraction (default 1.0) and the four fractions of qv, qc, th, qi (negative = inherit
+ *     tendency_fraction, options_obj.f90:1646-1649).  The values are looked at before the context.  With convection = 5 the call
+ *     allocates the slot's own arrays (ICAR_CU_*: CLDEFI = AVGEFI = 0.6 as BMJINIT leaves it, the rest 0), builds BMJINIT's nine
+ *     lookup tables on the host (SPLINE and all, with cp = 1012 and r_d = 287 as :236-237 passes them) into device memory and
+ *     allocates the column workspace: 16 arrays x min(kme - kms, 128) levels x min(nx ny, 65536) columns of REAL(4).  Kept out of
+ *     icar_hip_step_config so that the struct keeps its layout.
+ * icar_hip_cu_bmj == the call of BMJDRV (:434-465) alone on its..ite, jts..jte and the levels kts..kte-1 of
+ *     icar_hip_step_configure (kms..kme-1 without one): from TEMPERATURE (as diagnostic_update left it -- NOT recomputed from the
+ *     current potential temperature), the current WATER_VAPOR, PRESSURE, PRESSURE_INTERFACE, EXNER, DENSITY, DZ_INTERFACE, LAND_MASK
+ *     (never uploaded = all land) and ICAR_CU_CLDEFI -> ICAR_CU_TEND_TH = DTDT / exner, ICAR_CU_TEND_QV = DQDT / (1 - q)**2,
+ *     ICAR_CU_RAINCV = PCPCOL 1e3, ICAR_CU_CLDEFI, ICAR_CU_CUTOP, ICAR_CU_CUBOT of those columns; nothing else is touched.  Bit-identical
+ *     to the compiled reference.  NOT built: the bmj_rad_feedback block (cu_bmj.f90:267-351: CCLDFRA, QCCONV, QICONV, CONVCLD,
+ *     PRATEC) -- those arrays are private to cu_driver.f90, nothing reads them, and the block needs GAMMA() in REAL(4); W0AVG, which
+ *     BMJ never reads.  Levels: kts = 1 (BMJDRV's flip KFLIP = KTE+1-K and PSFC = PINT(i,1,j) assume it; with kts = 2 the reference
+ *     reads DTDT(1) below its lower bound, cu_bmj.f90:248), at least 3 levels kts..kte (with one scheme level the reference reads
+ *     PRSMID(LBOT+1) past the column, :755), at most 129; all refused before any launch.  A trial parcel whose cloud base cannot be
+ *     put PONE = 2500 Pa above the lowest level (a column thinner than 25 hPa; the reference reads level LMH+1 there) gets no CAPE.
+ * icar_hip_convect == convect(domain, options, dt) (:255-514) on the tile of icar_hip_step_configure: tend%th, tend%qv and RAINCV
+ *     zeroed over all i and k of memory on the rows jts..jte (:272-282), icar_hip_cu_bmj, then on those rows and all i, k of memory
+ *     x = x + (tend dt) fraction for WATER_VAPOR, CLOUD_WATER, POTENTIAL_TEMPERATURE, CLOUD_ICE whose fraction is > 0 when
+ *     tendency_fraction > 0 (BMJ leaves tend%qc and tend%qi at 0: those two get x + 0, the identity except that -0.0 becomes +0.0),
+ *     PRECIPITATION (REAL(8)) += RAINCV and ICAR_CU_ACC_CONV_PCP += RAINCV (:483-500).  Column-local on owned columns, in front of
+ *     mp(halo=1) and halo_send: an N-image run equals the one-image run in every owned cell.  icar_hip_substep / _step / _step_n
+ *     call it between pbl and the microphysics (time_step.f90:509) when dt > 1e-3.
+ * icar_hip_cu_reset: CLDEFI = AVGEFI, accumulated_convective_pcp = 0 (a restart of the slot).
+ * icar_hip_cu_upload / _download: the slot's own arrays by ICAR_CU_* (they have no field id): REAL(4), (nx,ny) but for the two
+ *     tendencies (nx,nz,ny).  icar_hip_cu_tables: QS0(134), SQS(134), PTBL(76,134), THE0(76), STHE(76), TTBL(134,76), THE0Q(152),
+ *     STHEQ(152), TTBLQ(440,152) one behind the other, Fortran element order; out may be NULL to query the count. */
+enum { ICAR_CU_BMJ = 5 };
+#define ICAR_CU_NO_STOCHASTIC (-9999.0f)
+enum icar_hip_cu_array {
+    ICAR_CU_CLDEFI = 0,            /* cu_driver.f90's CLDEFI: precipitation efficiency, carried from call to call */
+    ICAR_CU_ACC_CONV_PCP = 1,      /* domain%accumulated_convective_pcp%data_2d                                   */
+    ICAR_CU_RAINCV = 2,            /* cu_driver.f90's RAINCV of the last call (mm)                                */
+    ICAR_CU_CUTOP = 3,             /* CUTOP, CUBOT of the last call (level indices as REAL(4))                    */
+    ICAR_CU_CUBOT = 4,
+    ICAR_CU_TEND_TH = 5,           /* domain%tend%th (nx,nz,ny)                                                   */
+    ICAR_CU_TEND_QV = 6,           /* domain%tend%qv (nx,nz,ny)                                                   */
+    ICAR_CU_N = 7
+};
+int icar_hip_cu_configure(icar_hip_ctx *ctx, int convection, float stochastic_cu, float tendency_fraction, float tend_qv_fraction,
+                          float tend_qc_fraction, float tend_th_fraction, float tend_qi_fraction);
+int icar_hip_cu_bmj(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, int jte);
+int icar_hip_convect(icar_hip_ctx *ctx, float dt);
+int icar_hip_cu_reset(icar_hip_ctx *ctx);
+int icar_hip_cu_upload(icar_hip_ctx *ctx, int which, const void *host);
+int icar_hip_cu_download(icar_hip_ctx *ctx, int which, void *host);
+int icar_hip_cu_tables(icar_hip_ctx *ctx, float *out, size_t capacity, size_t *count);
+
 /* ---- T2: CFL reduction for compute_dt (src/main/time_step.f90:217-330, cfl_strictness 3) -----
  * out = max over the tile of max(|u_i|,|u_i+1|)/dx + max(|v_j|,|v_j+1|)/dx + max(|w_k|,|w_k-1|)/dz_levels(k) */
 int icar_hip_max_courant(icar_hip_ctx *ctx, float dx, const float *dz_levels, float *out);
@@ -520,7 +575,7 @@ int icar_hip_co_max(icar_hip_ctx *ctx, double *value);
  *   icar_hip_mp          == mp(domain, options, dt, halo, subset) (src/physics/mp_driver.f90:673-772) incl. the
  *                           update_interval gating (:698-713); halo / subset < 0 = argument not present
  *   icar_hip_advect_step == advect(domain, options, dt) (src/physics/advection_driver.f90:51-77)
- *   icar_hip_substep     == one pass of :474-539: diagnostic_update -> mp(halo=1) -> halo_send -> mp(subset=1) ->
+ *   icar_hip_substep     == one pass of :474-539: diagnostic_update -> [rad -> lsm -> pbl -> convect, each when configured] -> mp(halo=1) -> halo_send -> mp(subset=1) ->
  *                           halo_retrieve -> advect -> apply_forcing [-> enforce_limits], with the interior microphysics and
  *                           the streaming kernels issued on the context's second stream beside the heavy ones
  *   icar_hip_step        == step(domain, end_time, options) (:440-551); the model clock lives in the context.
@@ -571,7 +626,7 @@ int icar_hip_step_n(icar_hip_ctx *ctx, int nsteps, double *dt_last);
 
 /* ---- measurement helpers --------------------------------------------------------------------- */
 /* Average duration (ms) of the launches of a named kernel group since the last reset, measured
- * with HIP events on the context's stream (bench.py roofline block). group: "advect", "mp", "pbl", "rad", "diag_10m", "lsm_water", "lsm_fluxes" ... */
+ * with HIP events on the context's stream (bench.py roofline block). group: "advect", "mp", "pbl", "rad", "diag_10m", "lsm_water", "lsm_fluxes", "cu_bmj", "cu_stream" ... */
 int icar_hip_timing_enable(icar_hip_ctx *ctx, int on);
 /* restrict the timers to a comma-separated list of groups ("advect", "advect,mp,winds"; NULL or "" = all): every timed
  * scope costs its stream two timestamped barrier packets, ~5 us -- a dozen groups per sub-step are 10 % of a small tile's step */
