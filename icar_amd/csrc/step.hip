@@ -290,7 +290,9 @@ int icar_apply_forcing_run(icar_hip_ctx *c, double dt, const int *fields, const 
     ForceArgs a;
     for (int m = 0; m < n; ++m) {
         const int f = fields[m];
-        if (f < 0 || f >= ICAR_N_FIELD_SLOTS || f == ICAR_F_PRECIPITATION || f == ICAR_F_SNOWFALL || f == ICAR_F_GRAUPEL_ACC || f == ICAR_F_SURFACE_PRESSURE || f >= ICAR_F_TERRAIN) {
+        // (every id icar_field_count gives nx * ny elements: the kernel below walks nx * nz * ny of them)
+        if (f < 0 || f >= ICAR_N_FIELD_SLOTS || f == ICAR_F_PRECIPITATION || f == ICAR_F_SNOWFALL || f == ICAR_F_GRAUPEL_ACC || f == ICAR_F_SURFACE_PRESSURE
+            || (f >= ICAR_F_IVT && f <= ICAR_F_IWI) || f >= ICAR_F_TERRAIN) {
             icar_set_error("apply_forcing: only 3-D REAL(4) fields"); return 1;
         }
         a.x[m] = icar_field_f(c, f);
