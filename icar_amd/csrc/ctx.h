@@ -177,7 +177,7 @@ int icar_cu_copy(icar_hip_ctx *c, int which, void *host, bool to_device);
 int icar_cu_reset_run(icar_hip_ctx *c);
 int icar_cu_tables_copy(icar_hip_ctx *c, float *out, size_t capacity, size_t *n_out);
 // timestep.hip
-int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset);      // halo / subset < 0: argument not present
+int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset, bool exner_from_p = false);   // halo / subset < 0: argument not present
 int icar_update_dt(icar_hip_ctx *c, double *seconds);
 int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last = true);
 // halo_pack.hip
@@ -196,7 +196,8 @@ int icar_mass_conservative_acceleration(icar_hip_ctx *c, int update);
 int icar_iterative_winds_sweep(icar_hip_ctx *c, float dx, int nsweeps, int update);
 int icar_make_winds_grid_relative(icar_hip_ctx *c, int update);
 // step.hip
-enum { ICAR_DIAG_CELL = 4, ICAR_DIAG_FACE = 8, ICAR_DIAG_EXNER = 16, ICAR_DIAG_EXNER_RHO = 32 };     // finer parts of icar_diagnostic_update_run, internal
+enum { ICAR_DIAG_CELL = 4, ICAR_DIAG_FACE = 8, ICAR_DIAG_EXNER_RHO = 32 };     // finer parts of icar_diagnostic_update_run, internal
+enum { ICAR_LAZY_EXNER_IN_THOMPSON = -1 };     // timestep.hip (lazy_diag_part): no diagnostic launch, Thompson computes exner from the pressure
 int icar_diagnostic_update_run(icar_hip_ctx *c, int parts);
 bool icar_diag_columns_on(const icar_hip_ctx *c);      // column integrals (ivt, iwv, iwl, iwi) are computed on the device
 int icar_apply_forcing_run(icar_hip_ctx *c, double dt, const int *fields, const int *fb, int n, int w, int e, int s, int nn);
@@ -204,9 +205,9 @@ int icar_enforce_limits_run(icar_hip_ctx *c, const int *fields, int n);
 // mp_thompson.hip, thompson_tables.hip
 int icar_thompson_init_run(icar_hip_ctx *c, const float *params, const int *flags);
 int icar_thompson_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte,
-                      int ids, int ide, int jds, int jde, int kds, int kde);
+                      int ids, int ide, int jds, int jde, int kds, int kde, bool exner_from_p = false);
 int icar_thompson_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int (*tiles)[4], int kts, int kte,
-                            int ids, int ide, int jds, int jde, int kds, int kde);
+                            int ids, int ide, int jds, int jde, int kds, int kde, bool exner_from_p = false);
 int icar_thompson_prepare_constants(icar_hip_ctx *c);
 void icar_thompson_free(icar_hip_ctx *c);
 int icar_thompson_table_download(icar_hip_ctx *c, const char *name, double *out, size_t cap, size_t *n_out);

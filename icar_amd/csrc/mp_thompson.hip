@@ -20,6 +20,7 @@
 // in both layouts (memory order (i, k, j)).
 #include "ctx.h"
 #include "thompson_math.h"     // the level code's transcendentals and decade indices (shared with tests/support/th_probe.hip)
+#include "exner.h"
 #include "column_comm.h"
 #include <cmath>
 #include <cstdlib>
@@ -74,13 +75,20 @@ __device__ __forceinline__ float snow_poly_f(const float *s, float tc0, float b)
 
 #include "thompson_lane.inc"
 
+// A sub-step that hides its diagnostics launches no diagnostic kernel in front of this scheme (timestep.hip: lazy_diag_part); its
+// launches take exner_function (exner.h: the definition diagnostic_update's kernel uses) of the pressure they load anyway (EXP below)
+// instead of loading exner.
+
 // one column per wave (4 columns per 256-thread block), one level per lane; see thompson_lane.inc
-__global__ void __launch_bounds__(256, 4)   // 4 waves/SIMD (128 VGPRs, 252 B spill) measured best of 2..8: 7.2/6.0/5.6/6.2/6.3/9.2 ms
-k_thompson_lane(Dims d, const ThState *__restrict__ T, float *__restrict__ qv, float *__restrict__ qc, float *__restrict__ qr,
-                float *__restrict__ qi, float *__restrict__ qs, float *__restrict__ qg, float *__restrict__ ni, float *__restrict__ nr,
-                float *__restrict__ th, const float *__restrict__ pii, const float *__restrict__ p, const float *__restrict__ dz,
-                double *__restrict__ rain_acc, double *__restrict__ snow_acc, double *__restrict__ graupel_acc,
-                float dt, int i0, int i1, int j0, int k0, int nk)
+// EXP: exner from the pressure (exner_function) instead of loaded from pii
+#define TH_LANE_PARAMS Dims d, const ThState *__restrict__ T, float *__restrict__ qv, float *__restrict__ qc, float *__restrict__ qr, \
+                float *__restrict__ qi, float *__restrict__ qs, float *__restrict__ qg, float *__restrict__ ni, float *__restrict__ nr, \
+                float *__restrict__ th, const float *__restrict__ pii, const float *__restrict__ p, const float *__restrict__ dz, \
+                double *__restrict__ rain_acc, double *__restrict__ snow_acc, double *__restrict__ graupel_acc, \
+                float dt, int i0, int i1, int j0, int k0, int nk
+#define TH_LANE_ARGS d, T, qv, qc, qr, qi, qs, qg, ni, nr, th, pii, p, dz, rain_acc, snow_acc, graupel_acc, dt, i0, i1, j0, k0, nk
+template <bool EXP>
+__device__ __forceinline__ void thompson_lane_body(TH_LANE_PARAMS)
 {
     th_lds_init(threadIdx.x, blockDim.x);
     const int lane = threadIdx.x & 63;
@@ -89,7 +97,7 @@ k_thompson_lane(Dims d, const ThState *__restrict__ T, float *__restrict__ qv, f
     if (i > i1) return;                                   // wave-uniform
     const int kk = lane < nk ? lane : nk - 1;
     const int c = d.idx(i, k0 + kk, j);
-    const float pi_ = pii[c];
+    const float pi_ = EXP ? exner_function(p[c]) : pii[c];
     float t1d = th[c] * pi_, p1d = p[c], dz1d = dz[c], qv1d = qv[c], qc1d = qc[c], qi1d = qi[c], qr1d = qr[c], qs1d = qs[c],
           qg1d = qg[c], ni1d = ni[c], nr1d = nr[c];
     float pptrain = 0.f, pptsnow = 0.f, pptgraul = 0.f, pptice = 0.f;
@@ -110,6 +118,10 @@ k_thompson_lane(Dims d, const ThState *__restrict__ T, float *__restrict__ qv, f
         th[c] = t1d / pi_;
     }
 }
+__global__ void __launch_bounds__(256, 4)   // 4 waves/SIMD (128 VGPRs, 252 B spill) measured best of 2..8: 7.2/6.0/5.6/6.2/6.3/9.2 ms
+k_thompson_lane(TH_LANE_PARAMS) { thompson_lane_body<false>(TH_LANE_ARGS); }
+__global__ void __launch_bounds__(256, 4)
+k_thompson_lane_exp(TH_LANE_PARAMS) { thompson_lane_body<true>(TH_LANE_ARGS); }
 
 struct ThTiles { int n, i0[4], i1[4], j0[4], j1[4], tall[4], ib0[4], nbx[4], off[5], xcd_run; };
 // The leading arguments of k_thompson_pack as they lie in its kernel-argument segment (by-value parameters in order, each at its
@@ -129,17 +141,20 @@ static_assert(offsetof(ThPackArgs, T) == ((sizeof(Dims) + 7) & ~(size_t)7) && of
 // MAXT = largest block this instantiation is launched with.  Blocks of up to 512 threads (columns of up to 512 levels) get the
 // register budget of 3 waves per SIMD (168 VGPRs, no spills); at 128 VGPRs / 4 waves the kernel ran exactly as fast but spilled
 // 62 VGPRs -- 4 GB of scratch traffic per launch against 0.9 GB of algorithmic bytes.  1024-thread blocks need the 128.
-template <int MAXT>
 // Waves per SIMD of the 256-thread launch: until the DOUBLE PRECISION functions became glibc's (table look-ups from LDS: more
 // latency to hide, and no scalar registers held for polynomial coefficients any more) three waves at 168 VGPRs beat four at 128
 // (1.93 vs 1.98 ms); since then four win -- 1.77 against 1.86 ms alone, 3.10 against 3.15 ms per step at 512 x 512 x 40 (53 VGPRs
 // in scratch, no SGPR spills), equal on the small tiles (profiles/r04_steps.md).
-__global__ void __launch_bounds__(MAXT, 4)
-k_thompson_pack(Dims d, const ThState *__restrict__ T, float *__restrict__ qv, float *__restrict__ qc, float *__restrict__ qr,
-                float *__restrict__ qi, float *__restrict__ qs, float *__restrict__ qg, float *__restrict__ ni, float *__restrict__ nr,
-                float *__restrict__ th, const float *__restrict__ pii, const float *__restrict__ p, const float *__restrict__ dz,
-                double *__restrict__ rain_acc, double *__restrict__ snow_acc, double *__restrict__ graupel_acc,
-                float dt, ThTiles tl, int k0, int nk, int cpb)
+// EXP: exner from the pressure (exner_function) instead of loaded from pii; the body is one function, the entry points below
+// differ in nothing else
+#define TH_PACK_PARAMS Dims d, const ThState *__restrict__ T, float *__restrict__ qv, float *__restrict__ qc, float *__restrict__ qr, \
+                float *__restrict__ qi, float *__restrict__ qs, float *__restrict__ qg, float *__restrict__ ni, float *__restrict__ nr, \
+                float *__restrict__ th, const float *__restrict__ pii, const float *__restrict__ p, const float *__restrict__ dz, \
+                double *__restrict__ rain_acc, double *__restrict__ snow_acc, double *__restrict__ graupel_acc, \
+                float dt, ThTiles tl, int k0, int nk, int cpb
+#define TH_PACK_ARGS d, T, qv, qc, qr, qi, qs, qg, ni, nr, th, pii, p, dz, rain_acc, snow_acc, graupel_acc, dt, tl, k0, nk, cpb
+template <bool EXP>
+__device__ __forceinline__ void thompson_pack_body(TH_PACK_PARAMS)
 {
     extern __shared__ double lds_pack[];
     // several (its..ite, jts..jte) tiles in one launch (process_halo's four strips): block -> tile by prefix offsets
@@ -170,7 +185,7 @@ k_thompson_pack(Dims d, const ThState *__restrict__ T, float *__restrict__ qv, f
     const unsigned boff = (unsigned)c * 4u;
 #define TH_LD(p) (*(const float *)((const char *)(p) + boff))
 #define TH_ST(p, v) (*(float *)((char *)(p) + boff) = (v))
-    const float pi_ = TH_LD(pii);
+    const float pi_ = EXP ? exner_function(TH_LD(p)) : TH_LD(pii);
     float t1d = TH_LD(th) * pi_, p1d = TH_LD(p), dz1d = TH_LD(dz), qv1d = TH_LD(qv), qc1d = TH_LD(qc), qi1d = TH_LD(qi), qr1d = TH_LD(qr),
           qs1d = TH_LD(qs), qg1d = TH_LD(qg), ni1d = TH_LD(ni), nr1d = TH_LD(nr);
     float pptrain = 0.f, pptsnow = 0.f, pptgraul = 0.f, pptice = 0.f;
@@ -199,6 +214,12 @@ k_thompson_pack(Dims d, const ThState *__restrict__ T, float *__restrict__ qv, f
 #undef TH_LD
 #undef TH_ST
 }
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT, 4)
+k_thompson_pack(TH_PACK_PARAMS) { thompson_pack_body<false>(TH_PACK_ARGS); }
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT, 4)
+k_thompson_pack_exp(TH_PACK_PARAMS) { thompson_pack_body<true>(TH_PACK_ARGS); }
 
 __global__ void k_thompson_constants(ThState *T, float rg, float xslw1)
 {
@@ -225,8 +246,10 @@ int icar_thompson_prepare_constants(icar_hip_ctx *c)
     return 0;
 }
 
+// exner_from_p: the launches compute exner from the pressure instead of loading ICAR_F_EXNER (a sub-step whose diagnostic kernel was
+// left out, timestep.hip); the same values, so the same results
 int icar_thompson_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int (*tiles)[4], int kts, int kte,
-                            int ids, int ide, int jds, int jde, int kds, int kde)
+                            int ids, int ide, int jds, int jde, int kds, int kde, bool exner_from_p)
 {
     (void)ids; (void)jds; (void)kds; (void)kde;
     const ThState *T = icar_thompson_device_state(c);
@@ -268,12 +291,11 @@ int icar_thompson_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int (*t
             tl.tall[t] = (tl.i0[t] == tl.i1[t] && rows > 1) ? 1 : 0;
             tl.off[t + 1] = tl.off[t] + (tl.tall[t] ? (rows + cpb - 1) / cpb : tl.nbx[t] * rows);
         }
-        if (nt <= 512)
-            hipLaunchKernelGGL(k_thompson_pack<512>, dim3(tl.off[nt_]), dim3(nt), BlockComm::lds_bytes(nt, cpb), c->stream, c->d, T,
-                               qv, qc, qr, qi, qs, qg, ni, nr, th, pii, p, dz, pa, sa, ga, dt, tl, kts - c->kms, nk, cpb);
-        else
-            hipLaunchKernelGGL(k_thompson_pack<1024>, dim3(tl.off[nt_]), dim3(nt), BlockComm::lds_bytes(nt, cpb), c->stream, c->d, T,
-                               qv, qc, qr, qi, qs, qg, ni, nr, th, pii, p, dz, pa, sa, ga, dt, tl, kts - c->kms, nk, cpb);
+#define GO(K) hipLaunchKernelGGL(K, dim3(tl.off[nt_]), dim3(nt), BlockComm::lds_bytes(nt, cpb), c->stream, c->d, T, \
+                                 qv, qc, qr, qi, qs, qg, ni, nr, th, pii, p, dz, pa, sa, ga, dt, tl, kts - c->kms, nk, cpb)
+        if (nt <= 512) { if (exner_from_p) GO(k_thompson_pack_exp<512>); else GO(k_thompson_pack<512>); }
+        else           { if (exner_from_p) GO(k_thompson_pack_exp<1024>); else GO(k_thompson_pack<1024>); }
+#undef GO
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -281,16 +303,18 @@ int icar_thompson_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int (*t
     for (int t = 0; t < nt_; ++t) {                      // one column per wave, level = lane
         const int its = T4[t][0], i_end = T4[t][1], jts = T4[t][2], j_end = T4[t][3];
         dim3 gl((i_end - its + 1 + 3) / 4, j_end - jts + 1), bl(256);
-        hipLaunchKernelGGL(k_thompson_lane, gl, bl, 0, c->stream, c->d, T, qv, qc, qr, qi, qs, qg, ni, nr, th, pii, p, dz, pa, sa, ga,
-                           dt, its - c->ims, i_end - c->ims, jts - c->jms, kts - c->kms, nk);
+#define GO(K) hipLaunchKernelGGL(K, gl, bl, 0, c->stream, c->d, T, qv, qc, qr, qi, qs, qg, ni, nr, th, pii, p, dz, pa, sa, ga, \
+                                 dt, its - c->ims, i_end - c->ims, jts - c->jms, kts - c->kms, nk)
+        if (exner_from_p) GO(k_thompson_lane_exp); else GO(k_thompson_lane);
+#undef GO
     }
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 int icar_thompson_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte,
-                      int ids, int ide, int jds, int jde, int kds, int kde)
+                      int ids, int ide, int jds, int jde, int kds, int kde, bool exner_from_p)
 {
     const int tile[1][4] = {{its, ite, jts, jte}};
-    return icar_thompson_run_tiles(c, dt, 1, tile, kts, kte, ids, ide, jds, jde, kds, kde);
+    return icar_thompson_run_tiles(c, dt, 1, tile, kts, kte, ids, ide, jds, jde, kds, kde, exner_from_p);
 }

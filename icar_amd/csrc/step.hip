@@ -3,16 +3,11 @@
 // src/objects/domain_obj.f90:2383-2448, 2228-2243).  All HBM-bound, lanes along i.
 #include "ctx.h"
 #include "glibc_flt32.h"
+#include "exner.h"
 #include <cmath>
 
 namespace {
-constexpr float Rd = 287.058f, cp = 1012.0f;     // src/constants/icar_constants.f90:391-393
-
-// (p/po)**(Rd/cp): the C library's powf, bit for bit what the compiled reference computes (glibc_flt32.h)
-__device__ __forceinline__ float exner_function(float pressure)
-{   // atm_utilities.f90:682-691 ; po = 100000 (integer in the reference => p/100000.)
-    return gf_powf(pressure / 100000.0f, Rd / cp);
-}
+constexpr float Rd = ICAR_RD;
 
 // diagnostic_update's thermodynamics in two launches:
 //   k_diag_cell  exner, temperature, density of every cell (:87-101): one pow per cell, 2 arrays in, 3 out -- what the
@@ -22,8 +17,9 @@ __device__ __forceinline__ float exner_function(float pressure)
 //                the interior launch (timestep.hip).
 // T(k+-1) read back from memory is the same th * exner the cell kernel stored, so the split changes no result.
 // ST / SR: store temperature / density.  Inside icar_hip_step / _step_n a sub-step that is not the call's last one stores only
-// what something on the device reads before the next diagnostic_update (timestep.hip): exner always, density for the schemes
-// that read it; the values themselves are the same expressions either way.
+// what something on the device reads before the next diagnostic_update (timestep.hip): exner and density for the schemes that read
+// density (SR alone); the values themselves are the same expressions either way.  (Thompson alone reads neither from memory in such
+// a sub-step -- it computes exner from the pressure, mp_thompson.hip -- and this kernel is then not launched at all.)
 template <bool ST, bool SR>
 __global__ void __launch_bounds__(256)
 k_diag_cell(size_t n4, size_t n, const float *__restrict__ p, const float *__restrict__ th, float *__restrict__ exner,
@@ -207,8 +203,8 @@ k_enforce_limits(size_t n, LimitArgs a)
 // The sub-step splits 1 further: ICAR_DIAG_CELL (exner, T, density + the column integrals when they are on the device) before
 // the microphysics, ICAR_DIAG_FACE (interface values, mass-point winds) beside it; 1 = both.  With column integrals on the
 // device (they read the face kernel's outputs AND the water species) everything runs at ICAR_DIAG_CELL and _FACE is empty.
-// ICAR_DIAG_EXNER / ICAR_DIAG_EXNER_RHO: the cell kernel storing exner only / exner and density, for a sub-step whose other
-// diagnostics nothing can observe (timestep.hip decides; with column integrals on the device they are the full ICAR_DIAG_CELL).
+// ICAR_DIAG_EXNER_RHO: the cell kernel storing exner and density only, for a sub-step whose other diagnostics nothing can observe
+// (timestep.hip decides; with column integrals on the device it is the full ICAR_DIAG_CELL).
 bool icar_diag_columns_on(const icar_hip_ctx *c)
 {
     return c->field[ICAR_F_IVT] || c->field[ICAR_F_IWV] || c->field[ICAR_F_IWL] || c->field[ICAR_F_IWI];
@@ -218,20 +214,17 @@ int icar_diagnostic_update_run(icar_hip_ctx *c, int parts)
 {
     const float *u = (const float *)c->field[ICAR_F_U], *v = (const float *)c->field[ICAR_F_V];
     if (parts & 1) parts |= ICAR_DIAG_CELL | ICAR_DIAG_FACE;
-    if ((parts & (ICAR_DIAG_EXNER | ICAR_DIAG_EXNER_RHO)) && ((parts & ICAR_DIAG_CELL) || icar_diag_columns_on(c)))
-        parts = (parts & ~(ICAR_DIAG_EXNER | ICAR_DIAG_EXNER_RHO)) | ICAR_DIAG_CELL;
-    if (parts & (ICAR_DIAG_EXNER | ICAR_DIAG_EXNER_RHO)) {
+    if ((parts & ICAR_DIAG_EXNER_RHO) && ((parts & ICAR_DIAG_CELL) || icar_diag_columns_on(c)))
+        parts = (parts & ~ICAR_DIAG_EXNER_RHO) | ICAR_DIAG_CELL;
+    if (parts & ICAR_DIAG_EXNER_RHO) {
         const float *p = icar_field_f(c, ICAR_F_PRESSURE), *th = icar_field_f(c, ICAR_F_POTENTIAL_TEMPERATURE);
         float *ex = icar_field_f(c, ICAR_F_EXNER, false), *rho = icar_field_f(c, ICAR_F_DENSITY, false);
         if (!p || !th || !ex || !rho) return 1;
         ScopedTimer t(c, "diag");
         const size_t n4 = c->n3 / 4, rest = c->n3 - 4 * n4, nthr = n4 + rest;
         const dim3 g((unsigned)((nthr + 255) / 256)), b(256);
-        if (parts & ICAR_DIAG_EXNER_RHO) {
-            c->winds_valid = false;                              // density is rewritten, as below
-            hipLaunchKernelGGL((k_diag_cell<false, true>), g, b, 0, c->stream, n4, c->n3, p, th, ex, (float *)nullptr, rho);
-        } else
-            hipLaunchKernelGGL((k_diag_cell<false, false>), g, b, 0, c->stream, n4, c->n3, p, th, ex, (float *)nullptr, (float *)nullptr);
+        c->winds_valid = false;                                  // density is rewritten, as below
+        hipLaunchKernelGGL((k_diag_cell<false, true>), g, b, 0, c->stream, n4, c->n3, p, th, ex, (float *)nullptr, rho);
     }
     if (parts & (ICAR_DIAG_CELL | ICAR_DIAG_FACE)) {
     const float *p = icar_field_f(c, ICAR_F_PRESSURE), *th = icar_field_f(c, ICAR_F_POTENTIAL_TEMPERATURE);

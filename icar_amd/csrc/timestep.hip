@@ -23,8 +23,10 @@
 //   forcing of the advected scalars (boundary ring) <----- join
 //   enforce_limits (last two sub-steps)
 // Inside icar_hip_step / _step_n a sub-step that is not the call's last one leaves out the diagnostics nobody can observe
-// (lazy_diag_part below): with Thompson only exner is written, with mp_simple / WSM6 exner and density; k_diag_face and w_real run
-// in the call's last sub-step only.  Every single-sub-step entry point is its own last sub-step.
+// (lazy_diag_part below): with mp_simple / WSM6 exner and density are written; with Thompson NOTHING is -- no diagnostic launch in
+// front of the interior microphysics, whose launches (interior and strips) compute exner from the pressure they load anyway
+// (mp_thompson.hip: k_thompson_pack_exp, k_thompson_lane_exp; the same powf of the same quotient, so the same bits).  k_diag_face and
+// w_real run in the call's last sub-step only.  Every single-sub-step entry point is its own last sub-step and loads exner.
 #include "ctx.h"
 #include <chrono>
 #include "comm.h"
@@ -47,7 +49,8 @@ static bool cfg_ok(icar_hip_ctx *c, const char *who)
 }
 
 // ---- M0: mp(domain, options, dt, halo, subset) (mp_driver.f90:673-772) ------------------------------------------------
-static int process_subdomain(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte)
+// exner_from_p: Thompson computes exner from the pressure (a sub-step whose diagnostic kernel was left out, lazy_diag_part below)
+static int process_subdomain(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte, bool exner_from_p)
 {
     const icar_hip_step_config &g = c->step.cfg;
     if (ite < its || jte < jts) return 0;
@@ -55,13 +58,13 @@ static int process_subdomain(icar_hip_ctx *c, float dt, int its, int ite, int jt
     case kMP_SB04:     return icar_mp_simple_run(c, dt, its, ite, jts, jte, kts, kte, nullptr);
     case kMP_WSM6:     return icar_wsm6_run(c, dt, its, ite, jts, jte, kts, kte);
     case kMP_WSM3:     return icar_wsm3_run(c, dt, its, ite, jts, jte, kts, kte);
-    case kMP_THOMPSON: return icar_thompson_run(c, dt, its, ite, jts, jte, kts, kte, g.ids, g.ide, g.jds, g.jde, g.kds, g.kde);
+    case kMP_THOMPSON: return icar_thompson_run(c, dt, its, ite, jts, jte, kts, kte, g.ids, g.ide, g.jds, g.jde, g.kds, g.kde, exner_from_p);
     }
     icar_set_error("mp: microphysics option not built (1 Thompson, 2 mp_simple, 4 WSM6, 6 WSM3)");
     return 1;
 }
 
-int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset)
+int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset, bool exner_from_p)
 {
     const icar_hip_step_config &g = c->step.cfg;
     if (g.microphysics == 0) return 0;
@@ -78,7 +81,7 @@ int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset)
     int t[4][4];
     if (subset >= 0) {                                                                                     // :728-737
         icar_hip_mp_tiles(g.its, g.ite, g.jts, g.jte, 0, subset, t);
-        if (process_subdomain(c, mp_dt, t[0][0], t[0][1], t[0][2], t[0][3], g.kts, kte)) return 1;
+        if (process_subdomain(c, mp_dt, t[0][0], t[0][1], t[0][2], t[0][3], g.kts, kte, exner_from_p)) return 1;
     }
     if (halo >= 0) {                                                                                       // :721-726 -> process_halo :609-658
         const int n = icar_hip_mp_tiles(g.its, g.ite, g.jts, g.jte, halo, 0, t);
@@ -90,16 +93,16 @@ int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset)
         const bool batched = !overlapping && (g.microphysics == kMP_THOMPSON || g.microphysics == kMP_SB04 || g.microphysics == kMP_WSM6);
         if (batched && nl) {
             int r = 0;
-            if (g.microphysics == kMP_THOMPSON) r = icar_thompson_run_tiles(c, mp_dt, nl, live, g.kts, kte, g.ids, g.ide, g.jds, g.jde, g.kds, g.kde);
+            if (g.microphysics == kMP_THOMPSON) r = icar_thompson_run_tiles(c, mp_dt, nl, live, g.kts, kte, g.ids, g.ide, g.jds, g.jde, g.kds, g.kde, exner_from_p);
             else if (g.microphysics == kMP_WSM6) r = icar_wsm6_run_tiles(c, mp_dt, nl, live, g.kts, kte);
             else r = icar_mp_simple_run_tiles(c, mp_dt, nl, live, g.kts, kte, nullptr);
             if (r) return 1;
         } else if (!batched) {
-            for (int s = 0; s < n; ++s) if (process_subdomain(c, mp_dt, t[s][0], t[s][1], t[s][2], t[s][3], g.kts, kte)) return 1;
+            for (int s = 0; s < n; ++s) if (process_subdomain(c, mp_dt, t[s][0], t[s][1], t[s][2], t[s][3], g.kts, kte, exner_from_p)) return 1;
         }
     }
     if (halo < 0 && subset < 0)
-        if (process_subdomain(c, mp_dt, g.its, g.ite, g.jts, g.jte, g.kts, kte)) return 1;                 // :739-741
+        if (process_subdomain(c, mp_dt, g.its, g.ite, g.jts, g.jte, g.kts, kte, exner_from_p)) return 1;   // :739-741
     return 0;
 }
 
@@ -219,14 +222,16 @@ bool icar_substep_can_open_early(icar_hip_ctx *c)
 // icar_hip_step / _step_n run many sub-steps inside one library call, and the host cannot look between them: temperature,
 // density, the interface values, the mass-point winds and w_real of a sub-step that is not the call's last are seen by nobody
 // unless something on the device reads them before the next diagnostic_update rewrites them.  Who reads what:
-//   exner                 every microphysics scheme, ra_simple                        -> always written
+//   exner                 every microphysics scheme, ra_simple       -> written, except for Thompson alone, which then computes
+//                                                                       it from the pressure it loads anyway (mp_thompson.hip)
 //   density               mp_simple, WSM6, WSM3, pbl_simple, the Courant winds with advect_density
 //   temperature           the interface kernel (k_diag_face), lsm, BMJ
 //   pressure_interface    BMJ
 //   u_mass, v_mass, interface values   pbl_simple, the column integrals
 //   w_real                WSM3
-// Returns what the cell kernel of such a sub-step stores (ICAR_DIAG_EXNER / ICAR_DIAG_EXNER_RHO; its face kernel and w_real are
-// then left out), or 0: everything, as a single sub-step does.  When in doubt, everything (so with ra_simple on: it would do with
+// Returns what the cell kernel of such a sub-step stores (ICAR_DIAG_EXNER_RHO: exner and density), or ICAR_LAZY_EXNER_IN_THOMPSON:
+// nothing, no diagnostic launch at all -- exner alone would be left, and Thompson's launches of that sub-step make it themselves
+// (the face kernel and w_real are left out either way) -- or 0: everything, as a single sub-step does.  When in doubt, everything (so with ra_simple on: it would do with
 // exner, but which part suffices beside each microphysics scheme has not been measured or tested).
 static int lazy_diag_part(icar_hip_ctx *c, bool last)
 {
@@ -235,7 +240,7 @@ static int lazy_diag_part(icar_hip_ctx *c, bool last)
     if (c->step.boundarylayer == ICAR_PBL_SIMPLE || c->step.radiation == ICAR_RA_SIMPLE || g.advect_density || icar_diag_columns_on(c)) return 0;
     if (c->step.landsurface != 0) return 0;                                       // lsm reads temperature, density, the 10 m winds and ustar
     if (c->step.convection != 0) return 0;                                        // BMJ reads temperature, density and pressure_interface
-    if (g.microphysics == kMP_THOMPSON) return ICAR_DIAG_EXNER;                                   // reads exner, p, th, dz
+    if (g.microphysics == kMP_THOMPSON) return ICAR_LAZY_EXNER_IN_THOMPSON;                       // reads p, th, dz (and exner = f(p))
     if (g.microphysics == kMP_SB04 || g.microphysics == kMP_WSM6) return ICAR_DIAG_EXNER_RHO;     // ... and density
     return 0;                                                                                     // WSM3 (w_real, density), no microphysics
 }
@@ -244,10 +249,11 @@ static int substep_open(icar_hip_ctx *c, double dt, bool dt_known, bool &wreal_l
 {
     const icar_hip_step_config &g = c->step.cfg;
     const bool adv = (g.advection == ICAR_ADV_UPWIND || g.advection == ICAR_ADV_MPDATA);
+    const bool exner_from_p = lazy == ICAR_LAZY_EXNER_IN_THOMPSON;                // no diagnostic launch: Thompson makes exner itself
     wreal_later = false; face_later = false;
     if (g.diagnostics) {
         if (g.microphysics != kMP_WSM3) {
-            if (lazy) { if (icar_diagnostic_update_run(c, lazy)) return 1; }
+            if (lazy) { if (!exner_from_p && icar_diagnostic_update_run(c, lazy)) return 1; }
             else {
                 face_later = true;
                 if (icar_diagnostic_update_run(c, ICAR_DIAG_CELL)) return 1;
@@ -257,13 +263,13 @@ static int substep_open(icar_hip_ctx *c, double dt, bool dt_known, bool &wreal_l
     }
     if (icar_hip_aux_fork(c)) return 1;
     const double mp_last_before = c->step.mp_last_model_time;
-    if (icar_mp_run(c, dt, -1, 1)) return 1;                                      // :523 interior
+    if (icar_mp_run(c, dt, -1, 1, exner_from_p)) return 1;                        // :523 interior
     const double mp_last_after = c->step.mp_last_model_time;
     c->step.mp_last_model_time = mp_last_before;
     {
         AuxScope aux(c);
         if (aux.begin()) return 1;
-        if (icar_mp_run(c, dt, 1, -1)) return 1;                                  // :512 strips
+        if (icar_mp_run(c, dt, 1, -1, exner_from_p)) return 1;                    // :512 strips
         if (halo_send(c)) return 1;                                               // :515 pack + RCCL send / recv
         if (halo_retrieve(c)) return 1;                                           // :526 unpack, see icar_substep
         if (face_later && icar_diagnostic_update_run(c, ICAR_DIAG_FACE)) return 1;
@@ -313,6 +319,9 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
     const bool early = c->step.early_open;
     c->step.early_open = false;
     const int lazy = stepping ? lazy_diag_part(c, last) : 0;              // (dt <= 1e-3: diagnostic_update is all the pass does)
+    // Thompson alone: the only diagnostic such a sub-step still needs is exner, which both of its launches compute from the pressure
+    // (lazy_diag_part returns 0 with diagnostics off: the same condition as in substep_open)
+    const bool exner_from_p = !early && lazy == ICAR_LAZY_EXNER_IN_THOMPSON;
     if (early) {
         // the opening is in flight (substep_open_early); what it left out: the wind setup of the advect() below, on the second stream
         wreal_later = c->step.early_wreal; face_later = c->step.early_face;
@@ -329,7 +338,7 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
         if (g.microphysics != kMP_WSM3) {                                         // WSM3 reads w_real
             if (lazy) {
                 // not the call's last sub-step: only what the device reads before the next diagnostic_update (lazy_diag_part)
-                if (icar_diagnostic_update_run(c, lazy)) return 1;
+                if (!exner_from_p && icar_diagnostic_update_run(c, lazy)) return 1;
             } else {
             // exner / T / density now; the interface values and mass-point winds (nothing the microphysics reads or writes)
             // beside the interior launch below
@@ -357,9 +366,9 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
         // than 1 the message carries cells the interior pass has not touched yet (the reference sends them in that state,
         // time_step.f90:512-523).  Beside the interior launch the pack would read them while they are written, so this
         // configuration keeps the reference's order on one stream.
-        if (icar_mp_run(c, dt, 1, -1)) return 1;                                  // :512
+        if (icar_mp_run(c, dt, 1, -1, exner_from_p)) return 1;                    // :512
         if (halo_send(c)) return 1;                                               // :515
-        if (icar_mp_run(c, dt, -1, 1)) return 1;                                  // :523
+        if (icar_mp_run(c, dt, -1, 1, exner_from_p)) return 1;                    // :523
         if (face_later && icar_diagnostic_update_run(c, ICAR_DIAG_FACE)) return 1;
         if (halo_retrieve(c)) return 1;                                           // :526
     } else if (g.microphysics != 0) {
@@ -372,13 +381,13 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
         // work in front of it delayed the critical kernel by ~0.1 ms.  mp(halo=1) must still see the clock state it sees in the
         // reference's order (it runs before the interior pass moves last_model_time, :711-713), so that state is put back for it.
         const double mp_last_before = c->step.mp_last_model_time;
-        if (icar_mp_run(c, dt, -1, 1)) return 1;                                  // :523 interior
+        if (icar_mp_run(c, dt, -1, 1, exner_from_p)) return 1;                    // :523 interior
         const double mp_last_after = c->step.mp_last_model_time;
         c->step.mp_last_model_time = mp_last_before;
         {
             AuxScope aux(c);
             if (aux.begin()) return 1;
-            if (icar_mp_run(c, dt, 1, -1)) return 1;                              // :512 strips (the halo pass leaves last_model_time alone, :711)
+            if (icar_mp_run(c, dt, 1, -1, exner_from_p)) return 1;                // :512 strips (the halo pass leaves last_model_time alone, :711)
             if (halo_send(c)) return 1;                                           // :515 pack + RCCL send / recv
             // :526 halo_retrieve fills the cells OUTSIDE the owned tile; the microphysics is column-local and runs on owned
             // columns only, so the interior pass neither reads nor writes them: the unpack follows the receive on the second

@@ -5,7 +5,7 @@ sys.path.insert(0, ".")
 from icar_amd import build as B
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r06"
 want = {"mpdata.hip": ["k_mpdata_fused<5, true, true, true>", "k_mpdata_fused<5, true, true, false>", "k_mpdata_coef<false>"],
-        "mp_thompson.hip": ["k_thompson_pack<512>", "k_thompson_pack<1024>"], "cfl.hip": ["k_max_courant"], "advect.hip": None, "step.hip": None}
+        "mp_thompson.hip": ["k_thompson_pack<512>", "k_thompson_pack<1024>", "k_thompson_pack_exp<512>", "k_thompson_pack_exp<1024>"], "cfl.hip": ["k_max_courant"], "advect.hip": None, "step.hip": None}
 out = {"hipcc": subprocess.run([B.HIPCC, "--version"], capture_output=True, text=True).stdout.splitlines()[0]}
 for src, names in want.items():
     res = B.kernel_resources(src)
