@@ -31,6 +31,7 @@ SYMBOLS = [
     "icar_hip_linwinds_build_lut", "icar_hip_linwinds_build_lut_varying", "icar_hip_linwinds_lut_download", "icar_hip_linwinds_lut_upload", "icar_hip_linwinds_lut_entry",
     "icar_hip_linwinds_perturbation_download", "icar_hip_linwinds_perturbation_upload", "icar_hip_spatial_winds",
     "icar_hip_pbl_simple", "icar_hip_pbl_configure", "icar_hip_pbl", "icar_hip_pbl_nsubsteps",
+    "icar_hip_pbl_init", "icar_hip_ysu_sfc", "icar_hip_ysu", "icar_hip_ysu_upload", "icar_hip_ysu_download",
     "icar_hip_ra_simple", "icar_hip_rad_configure", "icar_hip_rad_calendar", "icar_hip_rad",
     "icar_hip_lsm_configure", "icar_hip_diag_10m", "icar_hip_water_simple", "icar_hip_apply_fluxes", "icar_hip_lsm", "icar_hip_lsm_layers",
     "icar_hip_cu_configure", "icar_hip_cu_bmj", "icar_hip_convect", "icar_hip_cu_reset", "icar_hip_cu_upload", "icar_hip_cu_download", "icar_hip_cu_tables",
@@ -105,6 +106,11 @@ def lib():
         L.icar_hip_pbl_configure.argtypes = [vp, ci]
         L.icar_hip_pbl.argtypes = [vp, ctypes.c_float]
         L.icar_hip_pbl_nsubsteps.argtypes = [vp, vp, ci]
+        L.icar_hip_pbl_init.argtypes = [vp, ci]
+        L.icar_hip_ysu_sfc.argtypes = [vp]
+        L.icar_hip_ysu.argtypes = [vp, ctypes.c_float, ci, ci, ci, ci, ci, ci]
+        L.icar_hip_ysu_upload.argtypes = [vp, ci, vp, ctypes.c_size_t]
+        L.icar_hip_ysu_download.argtypes = [vp, ci, vp, ctypes.c_size_t]
         L.icar_hip_ra_simple.argtypes = [vp, ctypes.c_float, ci, ci, ci, ci, ci, ci, ci]
         L.icar_hip_rad_configure.argtypes = [vp, ci]
         L.icar_hip_rad_calendar.argtypes = [vp, ci, ctypes.c_double, ctypes.c_double, ctypes.c_double]

@@ -27,6 +27,7 @@ struct Wsm3State;        // mp_wsm3.hip
 struct Wsm6State;        // mp_wsm6.hip
 struct IcarComm;         // comm.hip
 struct CuState;          // cu_bmj.hip
+struct YsuState;         // pbl_ysu.hip
 
 // state of the step driver (timestep.hip): the options / grid members the sub-step loop reads, the model clock, and what
 // mp_driver.f90 keeps in SAVE variables (last_model_time)
@@ -43,7 +44,7 @@ struct IcarStepState {
     bool early_lazy = false;                 // ... and that opening wrote only the diagnostics the device reads (not a call's last sub-step)
     bool failed = false;                 // a sub-step was abandoned half-applied (timestep.hip: update_dt_opened): the fields are not a model state any more
     bool winds_first = true;                 // wind.f90:297 `.not. allocated(domain%sintheta)`: update_winds has not run yet
-    int boundarylayer = 0;                   // options%physics%boundarylayer (icar_hip_pbl_configure): 0, 1 or ICAR_PBL_SIMPLE
+    int boundarylayer = 0;                   // options%physics%boundarylayer (icar_hip_pbl_configure / _pbl_init): 0, 1, ICAR_PBL_SIMPLE or ICAR_PBL_YSU
     int radiation = 0;                       // options%physics%radiation (icar_hip_rad_configure): 0, 1 or ICAR_RA_SIMPLE
     // icar_hip_rad_calendar: the calendar and, on the library's clock, 1 January 00:00 of the model time's year with the lengths of that year and the next
     bool rad_calendar_set = false;
@@ -109,6 +110,7 @@ struct icar_hip_ctx {
     float sfc_nz_thick = 0.0f;
     unsigned *sfc_levelmax = nullptr;
     CuState *cu = nullptr;               // cu_bmj.hip: the convection slot's arrays, BMJINIT's tables and the column workspace
+    YsuState *ysu = nullptr;             // pbl_ysu.hip: pbl_init's arrays, the scheme's results and tendencies, the column workspace
     // reductions / flags
     float *d_red = nullptr;              // small device scratch for reductions
     std::vector<float> dzl_host;         // dz_levels last uploaded behind d_red (compute_dt re-sends them only when they change)
@@ -157,6 +159,14 @@ int icar_mp_simple_run_tiles(icar_hip_ctx *c, float dt, int ntiles, const int ti
 int icar_pbl_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);
 int icar_pbl_run(icar_hip_ctx *c, float dt);                                // pbl(domain, options, dt): the configured scheme on the step's tile
 int icar_pbl_nsubsteps_copy(icar_hip_ctx *c, int *out, int n);
+inline bool icar_pbl_on(const icar_hip_ctx *c) { return c->step.boundarylayer == ICAR_PBL_SIMPLE || c->step.boundarylayer == ICAR_PBL_YSU; }   // pbl() does something
+// pbl_ysu.hip
+void icar_ysu_free(icar_hip_ctx *c);
+int icar_ysu_init_device(icar_hip_ctx *c);                                  // pbl_init for kPBL_YSU: arrays, z_atm, gz1oz0, zol, hol, workspace
+int icar_ysu_sfc_run(icar_hip_ctx *c, float dx);                            // pbl_driver.f90:227-254
+int icar_ysu_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);   // the call of ysu alone (kte the model's)
+int icar_ysu_pbl_run(icar_hip_ctx *c, float dt);                            // pbl(domain, options, dt) for kPBL_YSU on the step's tile
+int icar_ysu_copy(icar_hip_ctx *c, int which, void *host, size_t n, bool to_device);
 // ra_simple.hip
 int icar_ra_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte, int runlw, int calendar, double D, double year_days);
 int icar_rad_clock(icar_hip_ctx *c, double model_time, double *D, double *year_days);   // day of the year under icar_hip_rad_calendar's anchor

@@ -193,9 +193,10 @@ int icar_pbl_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, in
     return 0;
 }
 
-// pbl(domain, options, dt) (pbl_driver.f90:197-221): the configured scheme on the tile of icar_hip_step_configure
+// pbl(domain, options, dt) (pbl_driver.f90:197-354): the configured scheme on the tile of icar_hip_step_configure
 int icar_pbl_run(icar_hip_ctx *c, float dt)
 {
+    if (c->step.boundarylayer == ICAR_PBL_YSU) return icar_ysu_pbl_run(c, dt);      // :223-354, pbl_ysu.hip
     if (c->step.boundarylayer != ICAR_PBL_SIMPLE) return 0;            // (kPBL_BASIC: the reference's driver has no branch for it)
     const icar_hip_step_config &g = c->step.cfg;
     return icar_pbl_simple_run(c, dt, g.its, g.ite, g.jts, g.jte, g.kts, g.kte);

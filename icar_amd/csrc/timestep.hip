@@ -210,7 +210,7 @@ struct AuxScope {          // entry points called while this object lives launch
 bool icar_substep_can_open_early(icar_hip_ctx *c)
 {
     const icar_hip_step_config &g = c->step.cfg;
-    if (c->step.boundarylayer == ICAR_PBL_SIMPLE) return false;                   // pbl(domain, options, dt) opens the sub-step and takes dt
+    if (icar_pbl_on(c)) return false;                                             // pbl(domain, options, dt) opens the sub-step and takes dt
     if (c->step.radiation == ICAR_RA_SIMPLE) return false;                        // rad(domain, options, dt) likewise
     if (c->step.landsurface != 0) return false;                                   // lsm(domain, options, dt) likewise
     if (c->step.convection != 0) return false;                                    // convect(domain, options, dt) likewise
@@ -237,7 +237,7 @@ static int lazy_diag_part(icar_hip_ctx *c, bool last)
 {
     const icar_hip_step_config &g = c->step.cfg;
     if (last || !g.diagnostics) return 0;
-    if (c->step.boundarylayer == ICAR_PBL_SIMPLE || c->step.radiation == ICAR_RA_SIMPLE || g.advect_density || icar_diag_columns_on(c)) return 0;
+    if (icar_pbl_on(c) || c->step.radiation == ICAR_RA_SIMPLE || g.advect_density || icar_diag_columns_on(c)) return 0;   // (YSU reads temperature, u_mass, v_mass, pressure_interface, the 10 m winds and ustar)
     if (c->step.landsurface != 0) return 0;                                       // lsm reads temperature, density, the 10 m winds and ustar
     if (c->step.convection != 0) return 0;                                        // BMJ reads temperature, density and pressure_interface
     if (g.microphysics == kMP_THOMPSON) return ICAR_LAZY_EXNER_IN_THOMPSON;                       // reads p, th, dz (and exner = f(p))
@@ -313,7 +313,7 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
     const float dtf = (float)dt;
     const bool adv = (g.advection == ICAR_ADV_UPWIND || g.advection == ICAR_ADV_MPDATA);
     const bool stepping = dt > 1e-3;                                              // :483
-    const bool pbl = c->step.boundarylayer == ICAR_PBL_SIMPLE, rad = c->step.radiation == ICAR_RA_SIMPLE, lsm = c->step.landsurface != 0;
+    const bool pbl = icar_pbl_on(c), rad = c->step.radiation == ICAR_RA_SIMPLE, lsm = c->step.landsurface != 0;
     const bool cu = c->step.convection != 0;
     bool wreal_later = false, face_later = false, wreal_done = false;
     const bool early = c->step.early_open;
@@ -519,12 +519,54 @@ int icar_hip_mp_reset(icar_hip_ctx *c) { if (!c) { icar_set_error("mp_reset: nul
 
 int icar_hip_pbl_configure(icar_hip_ctx *c, int boundarylayer)
 {
-    // the value is looked at first: a host learns that YSU is not built without a device
-    if (boundarylayer == 3) { icar_set_error("pbl_configure: boundarylayer = 3 (kPBL_YSU) is not built; 0, 1 (kPBL_BASIC, nothing runs) or 2 (kPBL_SIMPLE)"); return 1; }
+    // the value is looked at first: a host learns without a device that YSU needs more than an option setter
+    if (boundarylayer == 3) {
+        icar_set_error("pbl_configure: boundarylayer = 3 (kPBL_YSU) needs pbl_init's arrays (z_atm, gz1oz0, the workspace), which pbl_configure has not built: "
+                       "call icar_hip_pbl_init(ctx, 3); pbl_configure takes 0, 1 (kPBL_BASIC, nothing runs) or 2 (kPBL_SIMPLE)");
+        return 1;
+    }
     if (boundarylayer < 0 || boundarylayer > 3) { icar_set_error("pbl_configure: boundarylayer is 0, 1 (kPBL_BASIC, nothing runs) or 2 (kPBL_SIMPLE)"); return 1; }
     if (!c) { icar_set_error("pbl_configure: null ctx"); return 1; }
     c->step.boundarylayer = boundarylayer;
     return 0;
+}
+
+// pbl_init(domain, options) (pbl_driver.f90:106-195)
+int icar_hip_pbl_init(icar_hip_ctx *c, int boundarylayer)
+{
+    if (boundarylayer < 0 || boundarylayer > ICAR_PBL_YSU) { icar_set_error("pbl_init: boundarylayer is 0, 1 (kPBL_BASIC, nothing runs), 2 (kPBL_SIMPLE) or 3 (kPBL_YSU)"); return 1; }
+    if (!c) { icar_set_error("pbl_init: null ctx"); return 1; }
+    if (boundarylayer != ICAR_PBL_YSU) { c->step.boundarylayer = boundarylayer; return 0; }     // what icar_hip_pbl_configure does
+    HIPCHK(hipSetDevice(c->device));
+    if (icar_ysu_init_device(c)) return 1;
+    c->step.boundarylayer = ICAR_PBL_YSU;
+    return 0;
+}
+
+int icar_hip_ysu_sfc(icar_hip_ctx *c)
+{
+    if (!c) { icar_set_error("ysu_sfc: null argument"); return 1; }
+    if (!cfg_ok(c, "ysu_sfc")) return 1;                                          // da_sfc_wtq reads domain%dx
+    HIPCHK(hipSetDevice(c->device));
+    return icar_ysu_sfc_run(c, c->step.cfg.dx);
+}
+
+int icar_hip_ysu(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte)
+{
+    if (icar_enter(c, "ysu")) return 1;
+    return icar_ysu_run(c, dt, its, ite, jts, jte, kts, kte);
+}
+
+int icar_hip_ysu_upload(icar_hip_ctx *c, int which, const void *host, size_t count)
+{
+    if (icar_enter(c, "ysu_upload", host != nullptr)) return 1;
+    return icar_ysu_copy(c, which, const_cast<void *>(host), count, true);
+}
+
+int icar_hip_ysu_download(icar_hip_ctx *c, int which, void *host, size_t count)
+{
+    if (icar_enter(c, "ysu_download", host != nullptr)) return 1;
+    return icar_ysu_copy(c, which, host, count, false);
 }
 
 int icar_hip_pbl(icar_hip_ctx *c, float dt)

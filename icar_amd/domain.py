@@ -30,7 +30,7 @@ class domain_t:
         self.device = int(device)
         self.exchange_vars = []          # kVARS names with an associated exchangeable (halo_send order)
         self._step_key = None            # what the library's step driver was last configured with (configure())
-        self._pbl_key = 0                # options%physics%boundarylayer as last handed to icar_hip_pbl_configure
+        self._pbl_key = 0                # options%physics%boundarylayer as last handed to icar_hip_pbl_configure / _pbl_init
         self._rad_key = 0                # options%physics%radiation as last handed to icar_hip_rad_configure
         self._lsm_key = (0, 0)           # options%physics%landsurface / %watersurface and lsm_options as last handed to icar_hip_lsm_configure
         self._cu_key = (0,)              # options%physics%convection and options%cu_options as last handed to icar_hip_cu_configure
@@ -70,7 +70,10 @@ class domain_t:
         p, g = options.parameters, self.grid
         bl = int(options.physics.boundarylayer if boundarylayer is None else boundarylayer)
         if bl != self._pbl_key:
-            check(lib().icar_hip_pbl_configure(self.ctx, bl), "icar_hip_pbl_configure")
+            if bl == 3:     # kPBL_YSU needs pbl_init's arrays (icar_amd.pbl.pbl_init): an option setter cannot make them
+                check(lib().icar_hip_pbl_init(self.ctx, bl), "icar_hip_pbl_init")
+            else:
+                check(lib().icar_hip_pbl_configure(self.ctx, bl), "icar_hip_pbl_configure")
             self._pbl_key = bl
         ra = int(options.physics.radiation if radiation is None else radiation)
         if ra != self._rad_key:

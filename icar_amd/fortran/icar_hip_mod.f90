@@ -21,6 +21,10 @@ module icar_hip
             hip_step_config_t, hip_step_configure, hip_update_dt, hip_compute_dt, hip_substep, hip_step, hip_step_n, hip_mp, hip_advect_step, hip_mp_reset, &
             hip_model_time, hip_set_model_time, hip_comm_unique_id, hip_comm_init, hip_comm_init_local, hip_comm_init_host, hip_comm_destroy, &
             hip_halo_send, hip_halo_retrieve, hip_co_min, hip_comm_ranks, hip_halo_selfcheck, hip_update_winds, hip_exchange_uv, hip_mpdata_exact, &
+            hip_pbl_init, hip_ysu_sfc, hip_ysu, hip_ysu_upload, hip_ysu_download, hip_ysu_download_kpbl, ICAR_PBL_YSU, &
+            ICAR_YSU_GROUND_SURF_TEMPERATURE, ICAR_YSU_HPBL, ICAR_YSU_KPBL, ICAR_YSU_EXCH_H, ICAR_YSU_PSIM, ICAR_YSU_PSIH, ICAR_YSU_REGIME, ICAR_YSU_RI, &
+            ICAR_YSU_WINDSPD, ICAR_YSU_HOL, ICAR_YSU_ZOL, ICAR_YSU_GZ1OZ0, ICAR_YSU_Z_ATM, ICAR_YSU_TEND_TH, ICAR_YSU_TEND_QV, ICAR_YSU_TEND_QC, &
+            ICAR_YSU_TEND_QI, ICAR_YSU_TEND_U, ICAR_YSU_TEND_V, ICAR_YSU_N, &
             hip_pbl_configure, hip_pbl, hip_pbl_simple, ICAR_PBL_SIMPLE, hip_rad_configure, hip_rad_calendar, hip_rad, hip_ra_simple, ICAR_RA_SIMPLE, &
             hip_lsm_configure, hip_diag_10m, hip_water_simple, hip_apply_fluxes, hip_lsm, hip_lsm_layers, ICAR_LSM_BASIC, ICAR_WATER_SIMPLE, &
             hip_cu_configure, hip_cu_bmj, hip_convect, hip_cu_reset, hip_cu_upload, hip_cu_download, ICAR_CU_BMJ, ICAR_CU_NO_STOCHASTIC, &
@@ -55,6 +59,13 @@ module icar_hip
   integer(c_int), parameter :: ICAR_LSM_BASIC = 1, ICAR_WATER_SIMPLE = 2     ! kLSM_BASIC, kWATER_SIMPLE, icar_constants.f90:358-365
   integer(c_int), parameter :: ICAR_RA_SIMPLE = 2       ! kRA_SIMPLE, icar_constants.f90
   integer(c_int), parameter :: ICAR_CU_BMJ = 5          ! kCU_BMJ, icar_constants.f90:345
+  integer(c_int), parameter :: ICAR_PBL_YSU = 3         ! kPBL_YSU, icar_constants.f90:356
+  ! enum icar_hip_ysu_array (include/icar_hip.h): the YSU scheme's own arrays, REAL(4) (nx,ny) but for exch_h and the six tendencies
+  ! (nx,nz,ny); ICAR_YSU_KPBL is INTEGER(4)
+  integer(c_int), parameter :: ICAR_YSU_GROUND_SURF_TEMPERATURE=0, ICAR_YSU_HPBL=1, ICAR_YSU_KPBL=2, ICAR_YSU_EXCH_H=3, ICAR_YSU_PSIM=4, &
+       ICAR_YSU_PSIH=5, ICAR_YSU_REGIME=6, ICAR_YSU_RI=7, ICAR_YSU_WINDSPD=8, ICAR_YSU_HOL=9, ICAR_YSU_ZOL=10, ICAR_YSU_GZ1OZ0=11, &
+       ICAR_YSU_Z_ATM=12, ICAR_YSU_TEND_TH=13, ICAR_YSU_TEND_QV=14, ICAR_YSU_TEND_QC=15, ICAR_YSU_TEND_QI=16, ICAR_YSU_TEND_U=17, &
+       ICAR_YSU_TEND_V=18, ICAR_YSU_N=19
   real(c_float), parameter :: ICAR_CU_NO_STOCHASTIC = -9999.0   ! kNO_STOCHASTIC, icar_constants.f90:340
   ! enum icar_hip_cu_array (include/icar_hip.h): the convection slot's own arrays, REAL(4) (nx,ny) but for the two tendencies (nx,nz,ny)
   integer(c_int), parameter :: ICAR_CU_CLDEFI=0, ICAR_CU_ACC_CONV_PCP=1, ICAR_CU_RAINCV=2, ICAR_CU_CUTOP=3, ICAR_CU_CUBOT=4, &
@@ -159,6 +170,21 @@ module icar_hip
      end function
      integer(c_int) function icar_hip_pbl(ctx, dt) bind(C, name="icar_hip_pbl")
        import; type(c_ptr), value :: ctx; real(c_float), value :: dt
+     end function
+     integer(c_int) function icar_hip_pbl_init(ctx, boundarylayer) bind(C, name="icar_hip_pbl_init")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: boundarylayer
+     end function
+     integer(c_int) function icar_hip_ysu_sfc(ctx) bind(C, name="icar_hip_ysu_sfc")
+       import; type(c_ptr), value :: ctx
+     end function
+     integer(c_int) function icar_hip_ysu(ctx, dt, its, ite, jts, jte, kts, kte) bind(C, name="icar_hip_ysu")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt; integer(c_int), value :: its, ite, jts, jte, kts, kte
+     end function
+     integer(c_int) function icar_hip_ysu_upload(ctx, which, host, count) bind(C, name="icar_hip_ysu_upload")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which; integer(c_size_t), value :: count
+     end function
+     integer(c_int) function icar_hip_ysu_download(ctx, which, host, count) bind(C, name="icar_hip_ysu_download")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which; integer(c_size_t), value :: count
      end function
      integer(c_int) function icar_hip_ra_simple(ctx, dt, its, ite, jts, jte, kts, kte, runlw) bind(C, name="icar_hip_ra_simple")
        import; type(c_ptr), value :: ctx; real(c_float), value :: dt; integer(c_int), value :: its, ite, jts, jte, kts, kte, runlw
@@ -435,14 +461,59 @@ contains
     call check(icar_hip_advect_step(ctx%p, dt), "advect_step")
   end subroutine
 
-  !> options%physics%boundarylayer for the sub-step loop: 0, 1 (kPBL_BASIC: nothing runs) or ICAR_PBL_SIMPLE; 3 (YSU) stops
+  !> options%physics%boundarylayer for the sub-step loop: 0, 1 (kPBL_BASIC: nothing runs) or ICAR_PBL_SIMPLE; 3 (YSU) stops: hip_pbl_init selects it
   subroutine hip_pbl_configure(ctx, boundarylayer)
     type(hip_ctx_t), intent(in) :: ctx
     integer, intent(in) :: boundarylayer
     call check(icar_hip_pbl_configure(ctx%p, int(boundarylayer,c_int)), "pbl_configure")
   end subroutine
 
-  !> pbl(domain, options, dt) (pbl_driver.f90:197-221) on the tile of hip_step_configure; dt = real(dt%seconds())
+  !> pbl_init(domain, options) (pbl_driver.f90:106-195): 0, 1, 2 as hip_pbl_configure; ICAR_PBL_YSU makes z_atm, gz1oz0, zol, hol from
+  !! ICAR_F_Z, ICAR_F_TERRAIN, ICAR_F_ROUGHNESS_Z0 (ICAR_F_LAND_MASK must be there too), zeroes the tendencies, allocates the workspace
+  subroutine hip_pbl_init(ctx, boundarylayer)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer, intent(in) :: boundarylayer
+    call check(icar_hip_pbl_init(ctx%p, int(boundarylayer,c_int)), "pbl_init")
+  end subroutine
+
+  !> pbl_driver.f90:227-254 alone: the 10 m wind speed with its floor, calc_Richardson_nr, da_sfc_wtq over the whole memory
+  subroutine hip_ysu_sfc(ctx)
+    type(hip_ctx_t), intent(in) :: ctx
+    call check(icar_hip_ysu_sfc(ctx%p), "ysu_sfc")
+  end subroutine
+
+  !> `call ysu(...)` alone (pbl_driver.f90:257-323); kte is the model's (lowered by one inside); the tendencies stay in place
+  subroutine hip_ysu(ctx, dt, its, ite, jts, jte, kts, kte)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    integer, intent(in) :: its, ite, jts, jte, kts, kte
+    call check(icar_hip_ysu(ctx%p, real(dt,c_float), int(its,c_int), int(ite,c_int), int(jts,c_int), int(jte,c_int), &
+                            int(kts,c_int), int(kte,c_int)), "ysu")
+  end subroutine
+
+  !> the scheme's own arrays by ICAR_YSU_*: a contiguous REAL(4) array of (nx,ny), or (nx,nz,ny) for exch_h and the tendencies
+  subroutine hip_ysu_upload(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(in), target, contiguous :: a(..)
+    call check(icar_hip_ysu_upload(ctx%p, which, c_loc(a), int(size(a),c_size_t)), "ysu_upload")
+  end subroutine
+
+  subroutine hip_ysu_download(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(inout), target, contiguous :: a(..)
+    call check(icar_hip_ysu_download(ctx%p, which, c_loc(a), int(size(a),c_size_t)), "ysu_download")
+  end subroutine
+
+  !> domain%kpbl (INTEGER) from ICAR_YSU_KPBL
+  subroutine hip_ysu_download_kpbl(ctx, kpbl)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(inout), target, contiguous :: kpbl(:,:)
+    call check(icar_hip_ysu_download(ctx%p, ICAR_YSU_KPBL, c_loc(kpbl), int(size(kpbl),c_size_t)), "ysu_download")
+  end subroutine
+
+  !> pbl(domain, options, dt) (pbl_driver.f90:197-354) on the tile of hip_step_configure; dt = real(dt%seconds())
   subroutine hip_pbl(ctx, dt)
     type(hip_ctx_t), intent(in) :: ctx
     real, intent(in) :: dt

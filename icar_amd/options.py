@@ -10,7 +10,7 @@ class physics_type:                      # opt_types.f90:15-24
     microphysics: int = 0
     advection: int = kADV_MPDATA
     windtype: int = 0
-    boundarylayer: int = 0               # 0, kPBL_BASIC (nothing runs), kPBL_SIMPLE (icar_amd.pbl)
+    boundarylayer: int = 0               # 0, kPBL_BASIC (nothing runs), kPBL_SIMPLE, kPBL_YSU (icar_amd.pbl)
     landsurface: int = 0                 # 0, kLSM_BASIC (icar_amd.surface); also read by pbl_var_request, as in the reference
     watersurface: int = 0                # 0, kWATER_BASIC (nothing runs), kWATER_SIMPLE (icar_amd.surface)
     radiation: int = 0                   # 0, kRA_BASIC (nothing runs), kRA_SIMPLE (icar_amd.radiation)

@@ -236,7 +236,8 @@ int icar_hip_wsm6_tiles(icar_hip_ctx *ctx, float dt, int ntiles, const int tiles
  *     kte+1 only receives the top flux; temperature and density are not re-diagnosed.  kte is lowered to kme-1 (:92); a
  *     call that leaves no half level (one level) is an error, and so are more than 1024 levels.
  * icar_hip_pbl_configure: options%physics%boundarylayer -- 0, 1 (kPBL_BASIC: pbl_driver.f90 has no branch for it, nothing
- *     runs) or ICAR_PBL_SIMPLE = kPBL_SIMPLE (icar_constants.f90:355); 3 (kPBL_YSU) is refused: not built.  With the scheme
+ *     runs) or ICAR_PBL_SIMPLE = kPBL_SIMPLE (icar_constants.f90:355); 3 (kPBL_YSU) is refused: it needs pbl_init's arrays, which an
+ *     option setter has not built -- icar_hip_pbl_init (P2) selects it.  With the scheme
  *     configured icar_hip_substep / _step / _step_n call pbl between diagnostic_update and the microphysics
  *     (time_step.f90:494) when dt > 1e-3 (:483).  Kept out of icar_hip_step_config so that the struct keeps its layout.
  * icar_hip_pbl == pbl(domain, options, dt) (pbl_driver.f90:197-221) with the tile bounds of icar_hip_step_configure.
@@ -247,6 +248,65 @@ int icar_hip_pbl_simple(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, 
 int icar_hip_pbl_configure(icar_hip_ctx *ctx, int boundarylayer);
 int icar_hip_pbl(icar_hip_ctx *ctx, float dt);
 int icar_hip_pbl_nsubsteps(icar_hip_ctx *ctx, int *nsubsteps, int nrows);
+
+/* ---- P2: the YSU boundary-layer scheme (src/physics/pbl_ysu.f90, src/utilities/pbl_utilities.f90, src/physics/pbl_driver.f90) -------
+ * icar_hip_pbl_init == pbl_init(domain, options) (pbl_driver.f90:106-195).  boundarylayer 0, 1, 2: what icar_hip_pbl_configure does.
+ *     ICAR_PBL_YSU = kPBL_YSU (icar_constants.f90): the YSU branch :127-194 from the context's Z, TERRAIN, ROUGHNESS_Z0 and LAND_MASK (a
+ *     missing upload is an error that names the field): ICAR_YSU_Z_ATM = z(:,kts,:) - terrain, ICAR_YSU_GZ1OZ0 = log(z_atm /
+ *     roughness_z0), ICAR_YSU_ZOL = 10, ICAR_YSU_HOL = 1000, the six tendencies and the scheme's results zeroed over the memory; on the
+ *     first call it allocates the slot's arrays (ICAR_YSU_*) and the column workspace, 19 arrays x min(kme - kms + 1, 129) levels x
+ *     min(nx ny, 131072) columns of REAL(4); then it selects the scheme.  The value is looked at before the context.
+ * icar_hip_ysu_sfc == pbl_driver.f90:227-254 alone, over the whole memory: ICAR_YSU_WINDSPD = sqrt(u_10m**2 + v_10m**2) with
+ *     `where(windspd==0) windspd=1e-5`, ICAR_YSU_RI = calc_Richardson_nr (atm_utilities.f90:1131-1139) from TEMPERATURE(:,1,:),
+ *     SKIN_TEMPERATURE and z_atm, then da_sfc_wtq (pbl_utilities.f90:69-544) -> ICAR_YSU_PSIM, _PSIH, _REGIME from SURFACE_PRESSURE,
+ *     ICAR_YSU_GROUND_SURF_TEMPERATURE (domain%ground_surf_temperature has no field id: upload it here; 0 until then), PRESSURE,
+ *     TEMPERATURE, U_MASS, V_MASS of level 1, z_atm, ROUGHNESS_Z0, LAND_MASK, USTAR and the dx of icar_hip_step_configure.  As the driver
+ *     writes it, da_sfc_wtq's qs is CLOUD_WATER(:,1,:) and its tg the ground temperature, while ysu gets the skin temperature.  Its
+ *     u10, v10, t2, q2 are dummies nothing reads and are not computed.  A cell with USTAR <= 0 gets the friction velocity the
+ *     reference computes before it has seen a positive one (its use_ust_wrf is a SAVEd variable: such a cell otherwise depends on
+ *     the cell visited before it).
+ * icar_hip_ysu == `call ysu(...)` (pbl_driver.f90:257-323; pbl_ysu.f90:16-262 with ysu2d :266-1152 and tridin :1154-1234) alone on
+ *     its..ite, jts..jte and the levels kts..kte-1 (kte is lowered by one here, as the driver lowers it): from U_MASS, V_MASS,
+ *     TEMPERATURE (as diagnostic_update left it), WATER_VAPOR, CLOUD_WATER, CLOUD_ICE, PRESSURE, PRESSURE_INTERFACE, EXNER, DZ_INTERFACE,
+ *     SURFACE_PRESSURE, ROUGHNESS_Z0, USTAR, LAND_MASK, SENSIBLE_HEAT, LATENT_HEAT / LH_vaporization, SKIN_TEMPERATURE, U_10M, V_10M and
+ *     icar_hip_ysu_sfc's results -> ICAR_YSU_HPBL, _KPBL, _HOL, _EXCH_H (levels kts..kte-2) and the six tendencies ICAR_YSU_TEND_*
+ *     (levels kts..kte-1), LEFT IN PLACE.  Bit-identical to the compiled reference.  Refused before any launch: kts /= 1 (ysu2d names
+ *     level 1 literally), fewer than 3 levels kts..kte (with one scheme level hpbl reads za(i,0), pbl_ysu.f90:655), more than 129.
+ * icar_hip_pbl (P1) == the whole YSU branch of pbl (:223-354) when YSU was initialised: icar_hip_ysu_sfc, icar_hip_ysu on the tile of
+ *     icar_hip_step_configure, then over the whole memory x = x + tend dt for WATER_VAPOR, CLOUD_WATER, POTENTIAL_TEMPERATURE, CLOUD_ICE
+ *     (where the tendency is 0 -- the top level, the halo -- x + 0: the identity except that -0.0 becomes +0.0) and the six
+ *     tendencies to 0.  The u / v tendencies are computed and thrown away, as in the reference (the statements applying them are
+ *     commented out there).  icar_hip_substep / _step / _step_n call it in the pbl slot (time_step.f90:494) when dt > 1e-3.
+ * icar_hip_ysu_upload / _download: the slot's own arrays by ICAR_YSU_* (they have no field id); count is checked against the array's
+ *     size: (nx,ny), (nx,nz,ny) for ICAR_YSU_EXCH_H and the tendencies; REAL(4) but ICAR_YSU_KPBL, which is INTEGER(4). */
+enum { ICAR_PBL_YSU = 3 };
+enum icar_hip_ysu_array {
+    ICAR_YSU_GROUND_SURF_TEMPERATURE = 0,   /* domain%ground_surf_temperature%data_2d (input)                     */
+    ICAR_YSU_HPBL = 1,             /* domain%hpbl%data_2d: boundary-layer height (m)                              */
+    ICAR_YSU_KPBL = 2,             /* domain%kpbl  INTEGER(4): level of the boundary-layer top                    */
+    ICAR_YSU_EXCH_H = 3,           /* domain%coeff_heat_exchange_3d%data_3d (nx,nz,ny)                            */
+    ICAR_YSU_PSIM = 4,             /* pbl_driver.f90's psim, psih, regime, Ri, windspd of the last call           */
+    ICAR_YSU_PSIH = 5,
+    ICAR_YSU_REGIME = 6,
+    ICAR_YSU_RI = 7,
+    ICAR_YSU_WINDSPD = 8,
+    ICAR_YSU_HOL = 9,              /* pbl_driver.f90's hol (1000 after pbl_init), zol (10, never changed)         */
+    ICAR_YSU_ZOL = 10,
+    ICAR_YSU_GZ1OZ0 = 11,          /* pbl_init's gz1oz0 and z_atm                                                 */
+    ICAR_YSU_Z_ATM = 12,
+    ICAR_YSU_TEND_TH = 13,         /* domain%tend%th_pbl, %qv_pbl, %qc_pbl, %qi_pbl, %u, %v (nx,nz,ny)            */
+    ICAR_YSU_TEND_QV = 14,
+    ICAR_YSU_TEND_QC = 15,
+    ICAR_YSU_TEND_QI = 16,
+    ICAR_YSU_TEND_U = 17,
+    ICAR_YSU_TEND_V = 18,
+    ICAR_YSU_N = 19
+};
+int icar_hip_pbl_init(icar_hip_ctx *ctx, int boundarylayer);
+int icar_hip_ysu_sfc(icar_hip_ctx *ctx);
+int icar_hip_ysu(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, int jte, int kts, int kte);
+int icar_hip_ysu_upload(icar_hip_ctx *ctx, int which, const void *host, size_t count);
+int icar_hip_ysu_download(icar_hip_ctx *ctx, int which, void *host, size_t count);
 
 /* ---- R1: the simple radiation scheme (src/physics/ra_simple.f90, src/physics/ra_driver.f90) --------------------------------
  * icar_hip_ra_simple == ra_simple(theta, pii, qv, qc, qs + qi + qg, qr, p, swdown, lwdown, cloud_cover, lat, lon, date, options,
