@@ -54,7 +54,7 @@ struct IcarStepState {
     int landsurface = 0, watersurface = 0, lsm_update_interval = 300;
     float sh_feedback_fraction = 0.625f, lh_feedback_fraction = 1.0f, sfc_layer_thickness = 400.0f;
     double lsm_last_model_time = -999.0;
-    // icar_hip_cu_configure: options%physics%convection (0 or ICAR_CU_BMJ) and options%cu_options with the fractions already inherited
+    // icar_hip_cu_configure: options%physics%convection (0, ICAR_CU_BMJ or ICAR_CU_TIEDTKE) and options%cu_options with the fractions already inherited
     int convection = 0;
     float cu_tendency_fraction = 1.0f, cu_tend_qv_fraction = 1.0f, cu_tend_qc_fraction = 1.0f, cu_tend_th_fraction = 1.0f, cu_tend_qi_fraction = 1.0f;
 };
@@ -186,6 +186,10 @@ int icar_convect_run(icar_hip_ctx *c, float dt);                            // c
 int icar_cu_copy(icar_hip_ctx *c, int which, void *host, bool to_device);
 int icar_cu_reset_run(icar_hip_ctx *c);
 int icar_cu_tables_copy(icar_hip_ctx *c, float *out, size_t capacity, size_t *n_out);
+// cu_tiedtke.hip
+int icar_tiedtke_init_device(icar_hip_ctx *c, const float *znu);           // init_convection for kCU_TIEDTKE: arrays, znu, workspace
+int icar_tiedtke_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);   // CU_TIEDTKE alone (kte the model's)
+int icar_tiedtke_copy(icar_hip_ctx *c, int which, void *host, bool to_device);
 // timestep.hip
 int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset, bool exner_from_p = false);   // halo / subset < 0: argument not present
 int icar_update_dt(icar_hip_ctx *c, double *seconds);

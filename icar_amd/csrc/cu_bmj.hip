@@ -1,4 +1,5 @@
-// icar_amd/csrc/cu_bmj.hip -- the convection slot (row C1) on gfx950: convect(domain, options, dt) as it runs for convection = kCU_BMJ.
+// icar_amd/csrc/cu_bmj.hip -- the convection slot (row C1) on gfx950: convect(domain, options, dt) as it runs for convection = kCU_BMJ
+// (and, around the scheme of cu_tiedtke.hip, for convection = kCU_TIEDTKE: the zeroing and the tendency loop are shared).
 //
 // Reference algorithm: src/physics/cu_driver.f90 -- init_convection :97-253 (XLAND :139-140, lowlyr = 1, bmj_rad_feedback, the call of
 // BMJINIT :230-243), convect :255-514 (the zeroing :272-282, the call of BMJDRV :434-465 on its..ite, jts..jte, kts..kte-1, the
@@ -7,7 +8,8 @@
 // made; stochastic_cu /= kNO_STOCHASTIC draws from random_number and is refused.
 //
 //   k_cu_zero    one thread per (i, j) of ims..ime, jts..jte marching k over the whole column: tend%th = tend%qv = 0, RAINCV = 0
-//                (tend%qc, %qi, %qs, %qr, %u, %v stay zero on this path and are not materialised)
+//                (tend%qs, %qr, %u, %v stay zero and are not materialised; tend%qc and %qi likewise with BMJ -- with Tiedtke,
+//                cu_tiedtke.hip, they exist and are zeroed here and applied by k_cu_apply like the other two)
 //   k_cu_load, k_cu_search, k_cu_bmj, k_cu_store
 //                ONE THREAD PER COLUMN of its..ite, lanes along i: the flipped column into the workspace (a streaming kernel), the
 //                buoyancy search and then the adjustment on the workspace, the two tendencies out of it (streaming) -- four launches, so that the scheme's kernels
@@ -47,14 +49,7 @@
 #define BMJ_WITH_TABLES
 #include "bmj_column.h"
 
-struct CuState {
-    float *arr[ICAR_CU_N] = {nullptr};
-    float *tables = nullptr;             // BMJ_TABLE_FLOATS
-    float *ws = nullptr;                 // BMJ_NARR x ws_levels x ws_cols
-    float *found = nullptr;              // 7 x ws_cols: what the search hands to the adjustment (BmjSearch)
-    size_t ws_cols = 0;
-    int ws_levels = 0;
-};
+#include "cu_state.h"
 
 namespace {
 constexpr size_t kWsColumns = (size_t)1 << 16;       // columns per launch of k_cu_bmj (a tile row always fits)
@@ -151,12 +146,17 @@ k_cu_store(CuArgs a)
 
 // cu_driver.f90:272-282 on the rows j0 .. j0+gridDim.y-1
 __global__ void __launch_bounds__(64)
-k_cu_zero(Dims d, int j0, float *__restrict__ tend_th, float *__restrict__ tend_qv, float *__restrict__ raincv)
+k_cu_zero(Dims d, int j0, float *__restrict__ tend_th, float *__restrict__ tend_qv, float *__restrict__ raincv, float *__restrict__ tend_qc,
+          float *__restrict__ tend_qi)
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = j0 + blockIdx.y;
     if (i >= d.nx) return;
     raincv[(size_t)d.nx * j + i] = 0.0f;
     size_t at = (size_t)d.idx(i, 0, j);
+    if (tend_qc) {                                                        // Tiedtke: tend%qc and tend%qi exist
+        for (int k = 0; k < d.nz; ++k, at += d.sk) { tend_th[at] = 0.0f; tend_qv[at] = 0.0f; tend_qc[at] = 0.0f; tend_qi[at] = 0.0f; }
+        return;
+    }
     for (int k = 0; k < d.nz; ++k, at += d.sk) { tend_th[at] = 0.0f; tend_qv[at] = 0.0f; }
 }
 
@@ -166,6 +166,7 @@ struct ApplyArgs {
     float dt, f_qv, f_qc, f_th, f_qi;    // a fraction <= 0 (or tendency_fraction <= 0): that field is left alone
     float *qv, *qc, *th, *qi;
     const float *tend_qv, *tend_th, *raincv;
+    const float *tend_qc, *tend_qi;      // null with BMJ, which leaves them at 0
     double *acc;
     float *acc_conv;
 };
@@ -183,6 +184,14 @@ k_cu_apply(ApplyArgs a)
     const int i = blockIdx.x * 64 + threadIdx.x, j = a.j0 + blockIdx.y;
     if (i >= a.d.nx) return;
     size_t at = (size_t)a.d.idx(i, 0, j);
+    if (a.tend_qc) {                                                                                  // Tiedtke: all four tendencies
+        for (int k = 0; k < a.d.nz; ++k, at += a.d.sk) {
+            if (a.f_qv > 0) a.qv[at] = a.qv[at] + a.tend_qv[at] * a.dt * a.f_qv;                      // :489
+            if (a.f_qc > 0) a.qc[at] = a.qc[at] + a.tend_qc[at] * a.dt * a.f_qc;                      // :490
+            if (a.f_th > 0) a.th[at] = a.th[at] + a.tend_th[at] * a.dt * a.f_th;                      // :491
+            if (a.f_qi > 0) a.qi[at] = a.qi[at] + a.tend_qi[at] * a.dt * a.f_qi;                      // :492
+        }
+    } else
     for (int k = 0; k < a.d.nz; ++k, at += a.d.sk) {
         if (a.f_qv > 0) a.qv[at] = a.qv[at] + a.tend_qv[at] * a.dt * a.f_qv;                          // :489
         if (a.f_qc > 0) add_zero(a.qc, at, a.dt, a.f_qc);                                             // :490, tend%qc == 0
@@ -211,7 +220,7 @@ float *need(icar_hip_ctx *c, int f, const char *who, const char *member)
 CuState *state(icar_hip_ctx *c, const char *who)
 {
     if (c->cu) return c->cu;
-    icar_set_error(std::string(who) + ": the convection slot is not configured (icar_hip_cu_configure with convection = 5)");
+    icar_set_error(std::string(who) + ": the convection slot is not configured (icar_hip_cu_configure with convection = 5, or icar_hip_cu_init)");
     return nullptr;
 }
 
@@ -262,12 +271,14 @@ void icar_cu_free(icar_hip_ctx *c)
     if (s->tables) hipFree(s->tables);
     if (s->ws) hipFree(s->ws);
     if (s->found) hipFree(s->found);
+    icar_tiedtke_free(s);
     delete s;
     c->cu = nullptr;
 }
 
 // init_convection (cu_driver.f90:97-253) for kCU_BMJ: the slot's arrays, BMJINIT's tables, the column workspace
-int icar_cu_init_device(icar_hip_ctx *c)
+// the slot's own arrays (ICAR_CU_*), shared by both schemes
+int icar_cu_common_init(icar_hip_ctx *c)
 {
     if (c->cu) return 0;
     CuState *s = new CuState();
@@ -277,7 +288,14 @@ int icar_cu_init_device(icar_hip_ctx *c)
         HIPCHK(hipMalloc(&s->arr[w], bytes));
         HIPCHK(hipMemsetAsync(s->arr[w], 0, bytes, c->stream));
     }
-    if (fill(c, s->arr[ICAR_CU_CLDEFI], count(c, ICAR_CU_CLDEFI), BMJ_AVGEFI)) return 1;              // BMJINIT :1880-1884
+    return fill(c, s->arr[ICAR_CU_CLDEFI], count(c, ICAR_CU_CLDEFI), BMJ_AVGEFI);                     // BMJINIT :1880-1884
+}
+
+int icar_cu_init_device(icar_hip_ctx *c)
+{
+    if (c->cu && c->cu->tables) return 0;
+    if (icar_cu_common_init(c)) return 1;
+    CuState *s = c->cu;
     std::vector<float> block(BMJ_TABLE_FLOATS);
     BmjTables h;
     bmj_build_tables(block.data(), &h);
@@ -299,6 +317,7 @@ int icar_cu_bmj_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jt
 {
     static const char *who = "cu_bmj";
     CuState *s = state(c, who);
+    if (s && !s->tables) { icar_set_error("cu_bmj: BMJ is not configured (icar_hip_cu_configure with convection = 5)"); return 1; }
     if (!s || levels_ok(c, s, kts, kte) || tile_ok(c, who, its, ite, jts, jte)) return 1;
     if (ite < its || jte < jts) return 0;
     CuArgs a;
@@ -341,7 +360,8 @@ int icar_convect_run(icar_hip_ctx *c, float dt)
     CuState *s = state(c, who);
     if (!s) return 1;
     const icar_hip_step_config &g = st.cfg;
-    if (levels_ok(c, s, g.kts, g.kte) || tile_ok(c, who, g.its, g.ite, g.jts, g.jte)) return 1;
+    const bool tdk = st.convection == ICAR_CU_TIEDTKE;
+    if ((tdk ? icar_tiedtke_levels_ok(c, g.kts, g.kte) : levels_ok(c, s, g.kts, g.kte)) || tile_ok(c, who, g.its, g.ite, g.jts, g.jte)) return 1;
     if (g.jte < g.jts) return 0;
     ApplyArgs a;
     const bool on = st.cu_tendency_fraction > 0;                      // :484
@@ -357,10 +377,12 @@ int icar_convect_run(icar_hip_ctx *c, float dt)
     const dim3 grid((c->d.nx + 63) / 64, g.jte - g.jts + 1), block(64);
     {
         ScopedTimer timer(c, "cu_stream");
-        hipLaunchKernelGGL(k_cu_zero, grid, block, 0, c->stream, c->d, g.jts - c->jms, s->arr[ICAR_CU_TEND_TH], s->arr[ICAR_CU_TEND_QV], s->arr[ICAR_CU_RAINCV]);
+        hipLaunchKernelGGL(k_cu_zero, grid, block, 0, c->stream, c->d, g.jts - c->jms, s->arr[ICAR_CU_TEND_TH], s->arr[ICAR_CU_TEND_QV], s->arr[ICAR_CU_RAINCV],
+                           tdk ? s->tdk[ICAR_TIEDTKE_TEND_QC] : nullptr, tdk ? s->tdk[ICAR_TIEDTKE_TEND_QI] : nullptr);
         HIPCHK(hipGetLastError());
     }
-    if (icar_cu_bmj_run(c, dt, g.its, g.ite, g.jts, g.jte, g.kts, g.kte)) return 1;
+    if (tdk ? icar_tiedtke_run(c, dt, g.its, g.ite, g.jts, g.jte, g.kts, g.kte) : icar_cu_bmj_run(c, dt, g.its, g.ite, g.jts, g.jte, g.kts, g.kte)) return 1;
+    a.tend_qc = tdk ? s->tdk[ICAR_TIEDTKE_TEND_QC] : nullptr; a.tend_qi = tdk ? s->tdk[ICAR_TIEDTKE_TEND_QI] : nullptr;
     a.d = c->d; a.j0 = g.jts - c->jms; a.dt = dt;
     a.tend_qv = s->arr[ICAR_CU_TEND_QV]; a.tend_th = s->arr[ICAR_CU_TEND_TH]; a.raincv = s->arr[ICAR_CU_RAINCV];
     a.acc_conv = s->arr[ICAR_CU_ACC_CONV_PCP];
@@ -396,6 +418,7 @@ int icar_cu_tables_copy(icar_hip_ctx *c, float *out, size_t capacity, size_t *n_
     if (!out) return 0;
     CuState *s = state(c, "cu_tables");
     if (!s) return 1;
+    if (!s->tables) { icar_set_error("cu_tables: BMJ is not configured (icar_hip_cu_configure with convection = 5)"); return 1; }
     if (capacity < (size_t)BMJ_TABLE_FLOATS) { icar_set_error("cu_tables: buffer too small"); return 1; }
     HIPCHK(hipMemcpyAsync(out, s->tables, sizeof(float) * BMJ_TABLE_FLOATS, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

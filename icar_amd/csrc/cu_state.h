@@ -1,0 +1,27 @@
+// icar_amd/csrc/cu_state.h -- what the convection slot keeps on the device, shared by cu_bmj.hip (the slot's driver and BMJ) and
+// cu_tiedtke.hip (the Tiedtke scheme).
+#pragma once
+#include "ctx.h"
+
+struct CuState {
+    float *arr[ICAR_CU_N] = {nullptr};
+    float *tables = nullptr;             // BMJ_TABLE_FLOATS (null until convection = 5 is configured)
+    float *ws = nullptr;                 // BMJ_NARR x ws_levels x ws_cols
+    float *found = nullptr;              // 7 x ws_cols: what the search hands to the adjustment (BmjSearch)
+    size_t ws_cols = 0;
+    int ws_levels = 0;
+    // Tiedtke (null until icar_hip_cu_init with convection = 1)
+    float *tdk[ICAR_TIEDTKE_N] = {nullptr};   // tend%qc, tend%qi (nx,nz,ny), PRATEC (nx,ny), KTYPE (nx,ny) INTEGER(4)
+    float *tdk_znu = nullptr;            // znu(kms:kme)
+    float *tdk_ws = nullptr;             // TDK_NARR x tdk_levels x tdk_cols
+    float *tdk_col = nullptr;            // TDK_NCOL x tdk_cols: the scalars a column carries between the launches
+    int *tdk_leveltop = nullptr;         // ny: the row's leveltop
+    size_t tdk_cols = 0;
+    int tdk_levels = 0;                  // levels of the workspace (scheme levels + 2)
+};
+
+// cu_bmj.hip
+int icar_cu_common_init(icar_hip_ctx *c);
+// cu_tiedtke.hip
+void icar_tiedtke_free(CuState *s);
+int icar_tiedtke_levels_ok(icar_hip_ctx *c, int kts, int kte);

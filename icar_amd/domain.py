@@ -34,6 +34,7 @@ class domain_t:
         self._rad_key = 0                # options%physics%radiation as last handed to icar_hip_rad_configure
         self._lsm_key = (0, 0)           # options%physics%landsurface / %watersurface and lsm_options as last handed to icar_hip_lsm_configure
         self._cu_key = (0,)              # options%physics%convection and options%cu_options as last handed to icar_hip_cu_configure
+        self.znu = None                  # domain%znu(kms:kme): the half sigma levels the Tiedtke scheme reads (load_case, or set by hand)
         self._forced, self._diagnostics, self._prefetch_dt = (), True, True
         if comm is not None:
             comm.attach(self)            # icar_hip_comm_init[_host]: collective over the images of the communicator
@@ -92,8 +93,9 @@ class domain_t:
         ckey = (0,) if cu == 0 or co is None else (cu, float(co.stochastic_cu), float(co.tendency_fraction)) + tuple(float(f) for f in co.resolved())
         if cu != 0 and co is None: ckey = (cu, -9999.0, 1.0, 1.0, 1.0, 1.0, 1.0)
         if ckey != self._cu_key:
-            from .convection import cu_configure
-            cu_configure(self, *ckey)
+            from .convection import cu_configure, cu_init
+            if cu == 1: cu_init(self, *ckey)      # kCU_TIEDTKE needs znu: icar_hip_cu_init
+            else: cu_configure(self, *ckey)
         adv = options.physics.advection if advection is None else advection
         adv_ids = tuple(KVARS[n][0] for n in ADVECTION_ORDER if options.vars_to_advect.get(n, 0) > 0)
         if forced is not None: self._forced = tuple((self.fid(n), int(bool(b))) for n, b in forced)
@@ -265,6 +267,8 @@ class domain_t:
         simple_pbl reads them; without a land_mask every cell is land; latitude and longitude, which ra_simple reads)."""
         alias = {"cloud_water": "cloud_water_mass", "rain": "rain_mass", "snow": "snow_mass",
                  "cloud_ice": "cloud_ice_mass", "graupel": "graupel_mass", "ice_number": "cloud_ice_number"}
+        if isinstance(case.get("znu"), np.ndarray):
+            self.znu = np.ascontiguousarray(case["znu"], np.float32)
         for k, v in case.items():
             name = alias.get(k, k)
             if isinstance(v, np.ndarray) and name in F.NAMES and v.ndim >= 2:

@@ -28,6 +28,8 @@ module icar_hip
             hip_pbl_configure, hip_pbl, hip_pbl_simple, ICAR_PBL_SIMPLE, hip_rad_configure, hip_rad_calendar, hip_rad, hip_ra_simple, ICAR_RA_SIMPLE, &
             hip_lsm_configure, hip_diag_10m, hip_water_simple, hip_apply_fluxes, hip_lsm, hip_lsm_layers, ICAR_LSM_BASIC, ICAR_WATER_SIMPLE, &
             hip_cu_configure, hip_cu_bmj, hip_convect, hip_cu_reset, hip_cu_upload, hip_cu_download, ICAR_CU_BMJ, ICAR_CU_NO_STOCHASTIC, &
+            hip_cu_init, hip_cu_tiedtke, hip_tiedtke_upload, hip_tiedtke_download, hip_tiedtke_download_ktype, ICAR_CU_TIEDTKE, &
+            ICAR_TIEDTKE_TEND_QC, ICAR_TIEDTKE_TEND_QI, ICAR_TIEDTKE_PRATEC, ICAR_TIEDTKE_KTYPE, ICAR_TIEDTKE_N, &
             ICAR_CU_CLDEFI, ICAR_CU_ACC_CONV_PCP, ICAR_CU_RAINCV, ICAR_CU_CUTOP, ICAR_CU_CUBOT, ICAR_CU_TEND_TH, ICAR_CU_TEND_QV, ICAR_CU_N, &
             ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_SELF, ICAR_N_ADVECTABLE
   public :: ICAR_F_WATER_VAPOR, ICAR_F_CLOUD_WATER, ICAR_F_RAIN, ICAR_F_SNOW, ICAR_F_POTENTIAL_TEMPERATURE, &
@@ -70,6 +72,9 @@ module icar_hip
   ! enum icar_hip_cu_array (include/icar_hip.h): the convection slot's own arrays, REAL(4) (nx,ny) but for the two tendencies (nx,nz,ny)
   integer(c_int), parameter :: ICAR_CU_CLDEFI=0, ICAR_CU_ACC_CONV_PCP=1, ICAR_CU_RAINCV=2, ICAR_CU_CUTOP=3, ICAR_CU_CUBOT=4, &
        ICAR_CU_TEND_TH=5, ICAR_CU_TEND_QV=6, ICAR_CU_N=7
+  integer(c_int), parameter :: ICAR_CU_TIEDTKE = 1      ! kCU_TIEDTKE, icar_constants.f90
+  ! enum icar_hip_tiedtke_array: the Tiedtke scheme's own arrays: tend%qc, tend%qi (nx,nz,ny), PRATEC (nx,ny) REAL(4), KTYPE (nx,ny) INTEGER(4)
+  integer(c_int), parameter :: ICAR_TIEDTKE_TEND_QC=0, ICAR_TIEDTKE_TEND_QI=1, ICAR_TIEDTKE_PRATEC=2, ICAR_TIEDTKE_KTYPE=3, ICAR_TIEDTKE_N=4
 
   !> struct icar_hip_step_config == the members of options_t / grid_t the sub-step loop reads (time_step.f90:440-551)
   type, bind(C) :: hip_step_config_t
@@ -236,6 +241,20 @@ module icar_hip
        import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
      end function
      integer(c_int) function icar_hip_cu_download(ctx, which, host) bind(C, name="icar_hip_cu_download")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
+     end function
+     integer(c_int) function icar_hip_cu_init(ctx, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, &
+                                              tend_th_fraction, tend_qi_fraction, znu) bind(C, name="icar_hip_cu_init")
+       import; type(c_ptr), value :: ctx, znu; integer(c_int), value :: convection
+       real(c_float), value :: stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction
+     end function
+     integer(c_int) function icar_hip_cu_tiedtke(ctx, dt, its, ite, jts, jte) bind(C, name="icar_hip_cu_tiedtke")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt; integer(c_int), value :: its, ite, jts, jte
+     end function
+     integer(c_int) function icar_hip_tiedtke_upload(ctx, which, host) bind(C, name="icar_hip_tiedtke_upload")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
+     end function
+     integer(c_int) function icar_hip_tiedtke_download(ctx, which, host) bind(C, name="icar_hip_tiedtke_download")
        import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
      end function
      integer(c_int) function icar_hip_wsm6_init(ctx) bind(C, name="icar_hip_wsm6_init")
@@ -610,7 +629,7 @@ contains
     nz = int(n)
   end function
 
-  !> init_convection (cu_driver.f90:97-253): options%physics%convection (0 or ICAR_CU_BMJ; Tiedtke and NSAS are not built, 2 and 3 have no
+  !> init_convection (cu_driver.f90:97-253): options%physics%convection (0 or ICAR_CU_BMJ; Tiedtke goes through hip_cu_init, NSAS is not built, 2 and 3 have no
   !! branch in the reference) and options%cu_options (stochastic_cu must be kNO_STOCHASTIC; a negative fraction inherits tendency_fraction)
   subroutine hip_cu_configure(ctx, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction)
     type(hip_ctx_t), intent(in) :: ctx
@@ -655,6 +674,47 @@ contains
     integer(c_int), intent(in) :: which
     real(c_float), intent(inout), target, contiguous :: a(..)
     call check(icar_hip_cu_download(ctx%p, which, c_loc(a)), "cu_download")
+  end subroutine
+
+  !> init_convection with every scheme that is built: 0 and ICAR_CU_BMJ as hip_cu_configure; ICAR_CU_TIEDTKE takes domain%znu(kms:kme)
+  subroutine hip_cu_init(ctx, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction, znu)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer, intent(in) :: convection
+    real, intent(in) :: stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction
+    real(c_float), intent(in), target, contiguous :: znu(:)
+    call check(icar_hip_cu_init(ctx%p, int(convection,c_int), real(stochastic_cu,c_float), real(tendency_fraction,c_float), &
+                                real(tend_qv_fraction,c_float), real(tend_qc_fraction,c_float), real(tend_th_fraction,c_float), &
+                                real(tend_qi_fraction,c_float), c_loc(znu)), "cu_init")
+  end subroutine
+
+  !> the call of CU_TIEDTKE alone (cu_driver.f90:303-330) on a range of columns
+  subroutine hip_cu_tiedtke(ctx, dt, its, ite, jts, jte)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    integer, intent(in) :: its, ite, jts, jte
+    call check(icar_hip_cu_tiedtke(ctx%p, real(dt,c_float), int(its,c_int), int(ite,c_int), int(jts,c_int), int(jte,c_int)), "cu_tiedtke")
+  end subroutine
+
+  !> the Tiedtke scheme's REAL(4) arrays by ICAR_TIEDTKE_*: (nx,nz,ny) for the two tendencies, (nx,ny) for PRATEC
+  subroutine hip_tiedtke_upload(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(in), target, contiguous :: a(..)
+    call check(icar_hip_tiedtke_upload(ctx%p, which, c_loc(a)), "tiedtke_upload")
+  end subroutine
+
+  subroutine hip_tiedtke_download(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(inout), target, contiguous :: a(..)
+    call check(icar_hip_tiedtke_download(ctx%p, which, c_loc(a)), "tiedtke_download")
+  end subroutine
+
+  !> KTYPE (nx,ny) INTEGER(4) of the last call
+  subroutine hip_tiedtke_download_ktype(ctx, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(inout), target, contiguous :: a(:,:)
+    call check(icar_hip_tiedtke_download(ctx%p, ICAR_TIEDTKE_KTYPE, c_loc(a)), "tiedtke_download")
   end subroutine
 
   subroutine hip_mp_reset(ctx)

@@ -385,8 +385,8 @@ int icar_hip_lsm_layers(icar_hip_ctx *ctx, int *nz);
 
 /* ---- C1: the convection slot (src/physics/cu_driver.f90 with convection = kCU_BMJ, src/physics/cu_bmj.f90) ---------------------------
  * icar_hip_cu_configure: init_convection (cu_driver.f90:97-253) -- options%physics%convection and options%cu_options.
- *     convection: 0 (convect returns at once, :264) or ICAR_CU_BMJ = kCU_BMJ (icar_constants.f90:345).  1 (kCU_TIEDTKE) and 4 (kCU_NSAS)
- *     are refused: not built.  2 (kCU_SIMPLE) is refused: cu_driver.f90 has no branch for it and cu_simple.f90 is not among the
+ *     convection: 0 (convect returns at once, :264) or ICAR_CU_BMJ = kCU_BMJ (icar_constants.f90:345).  1 (kCU_TIEDTKE) is refused here:
+ *     it needs znu, which icar_hip_cu_init (C2) takes.  4 (kCU_NSAS) is refused: not built.  2 (kCU_SIMPLE) is refused: cu_driver.f90 has no branch for it and cu_simple.f90 is not among the
  *     reference's objects; 3 (kCU_KAINFR) likewise: its branch in cu_driver.f90 is commented out and cu_kf.f90 is not built.
  *     stochastic_cu: ICAR_CU_NO_STOCHASTIC = kNO_STOCHASTIC (-9999); anything else draws from random_number in the reference
  *     (:287-295) and is refused.  tendency_fraction (default 1.0) and the four fractions of qv, qc, th, qi (negative = inherit
@@ -437,6 +437,44 @@ int icar_hip_cu_reset(icar_hip_ctx *ctx);
 int icar_hip_cu_upload(icar_hip_ctx *ctx, int which, const void *host);
 int icar_hip_cu_download(icar_hip_ctx *ctx, int which, void *host);
 int icar_hip_cu_tables(icar_hip_ctx *ctx, float *out, size_t capacity, size_t *count);
+
+/* ---- C2: the Tiedtke scheme in the convection slot (cu_driver.f90 with convection = kCU_TIEDTKE, src/physics/cu_tiedtke.f90) ----------
+ * icar_hip_cu_init == init_convection(domain, options) (cu_driver.f90:97-253) with every scheme that is built.  convection 0 or
+ *     ICAR_CU_BMJ: exactly icar_hip_cu_configure (znu may be NULL).  ICAR_CU_TIEDTKE = kCU_TIEDTKE (icar_constants.f90): znu is
+ *     domain%znu(kms:kme), copied; the call allocates tend%qc, tend%qi, PRATEC and KTYPE (ICAR_TIEDTKE_*, zero as tiedtkeinit leaves
+ *     them), the slot's ICAR_CU_* arrays and the column workspace: 25 arrays x (min(kme - kms, 128) + 2) levels x min(nx ny, 65536)
+ *     columns of REAL(4), and 16 values per column beside it.  4, 2, 3, a stochastic_cu other than ICAR_CU_NO_STOCHASTIC and a NaN
+ *     are refused as by icar_hip_cu_configure; the values are looked at before the context.
+ * icar_hip_cu_tiedtke == the call of CU_TIEDTKE (:303-330) alone on its..ite, jts..jte and the levels kts..kte-1 of
+ *     icar_hip_step_configure (kms..kme-1 without one), with itimestep = STEPCU = 1: from TEMPERATURE (as diagnostic_update left
+ *     it), WATER_VAPOR, CLOUD_WATER, CLOUD_ICE, EXNER, DENSITY, W_REAL (W0AVG without the stochastic term), DZ_INTERFACE, PRESSURE,
+ *     PRESSURE_INTERFACE, LAND_MASK (never uploaded = all land; XLAND = 2 where the mask is 0 or 2) and znu -> ICAR_CU_TEND_TH,
+ *     ICAR_CU_TEND_QV, ICAR_TIEDTKE_TEND_QC, ICAR_TIEDTKE_TEND_QI, ICAR_CU_RAINCV, ICAR_TIEDTKE_PRATEC and ICAR_TIEDTKE_KTYPE of
+ *     those columns; nothing else is touched.  Bit-identical to the compiled reference.  With itimestep = 1 the moisture
+ *     convergence PQTE is zero on entry, so no column is ever of KTYPE 1 or 2: convection starts at mid level (CUBASMC, KTYPE 3) or
+ *     not at all, and LATENT_HEAT, SENSIBLE_HEAT and the winds are read by nothing that is evaluated (icar_amd/csrc/tiedtke_column.h
+ *     has the derivation); tend%u / tend%v (CUDUDV) are not built: convect applies neither (:502-507 is commented out).
+ *     `leveltop`, the level above which mid-level convection may not start, is made once per row from the pressure of column its,
+ *     as the reference makes it from the first column of its tile row: an N-image run may differ from the one-image run there,
+ *     in the reference and here.  Levels: kts = 1, at least 4 levels kts..kte (with two scheme levels the reference reads
+ *     PAPH(JL,0), cu_tiedtke.f90:937), at most 129; all refused before any launch.
+ * icar_hip_convect / _substep / _step / _step_n run this scheme when icar_hip_cu_init selected it: tend%qc and tend%qi are zeroed
+ *     and applied like the other two, and the whole of diagnostic_update, w_real included, precedes convect in the sub-step.
+ * icar_hip_tiedtke_upload / _download: the scheme's own arrays by ICAR_TIEDTKE_*: the two tendencies (nx,nz,ny) and PRATEC (nx,ny)
+ *     REAL(4), KTYPE (nx,ny) INTEGER(4): the column's final KTYPE (0 or 3). */
+enum { ICAR_CU_TIEDTKE = 1 };
+enum icar_hip_tiedtke_array {
+    ICAR_TIEDTKE_TEND_QC = 0,      /* domain%tend%qc (nx,nz,ny)                                                   */
+    ICAR_TIEDTKE_TEND_QI = 1,      /* domain%tend%qi (nx,nz,ny)                                                   */
+    ICAR_TIEDTKE_PRATEC = 2,       /* cu_driver.f90's PRATEC of the last call (mm/s)                              */
+    ICAR_TIEDTKE_KTYPE = 3,        /* KTYPE of the last call, INTEGER(4)                                          */
+    ICAR_TIEDTKE_N = 4
+};
+int icar_hip_cu_init(icar_hip_ctx *ctx, int convection, float stochastic_cu, float tendency_fraction, float tend_qv_fraction,
+                     float tend_qc_fraction, float tend_th_fraction, float tend_qi_fraction, const float *znu);
+int icar_hip_cu_tiedtke(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, int jte);
+int icar_hip_tiedtke_upload(icar_hip_ctx *ctx, int which, const void *host);
+int icar_hip_tiedtke_download(icar_hip_ctx *ctx, int which, void *host);
 
 /* ---- T2: CFL reduction for compute_dt (src/main/time_step.f90:217-330, cfl_strictness 3) -----
  * out = max over the tile of max(|u_i|,|u_i+1|)/dx + max(|v_j|,|v_j+1|)/dx + max(|w_k|,|w_k-1|)/dz_levels(k) */
