@@ -36,6 +36,7 @@ SYMBOLS = [
     "icar_hip_lsm_configure", "icar_hip_diag_10m", "icar_hip_water_simple", "icar_hip_apply_fluxes", "icar_hip_lsm", "icar_hip_lsm_layers",
     "icar_hip_cu_configure", "icar_hip_cu_bmj", "icar_hip_convect", "icar_hip_cu_reset", "icar_hip_cu_upload", "icar_hip_cu_download", "icar_hip_cu_tables",
     "icar_hip_cu_init", "icar_hip_cu_tiedtke", "icar_hip_tiedtke_upload", "icar_hip_tiedtke_download",
+    "icar_hip_convection_init", "icar_hip_cu_nsas", "icar_hip_nsas_upload", "icar_hip_nsas_download",
 ]
 
 
@@ -134,6 +135,10 @@ def lib():
         L.icar_hip_cu_tiedtke.argtypes = [vp, cf, ci, ci, ci, ci]
         L.icar_hip_tiedtke_upload.argtypes = [vp, ci, vp]
         L.icar_hip_tiedtke_download.argtypes = [vp, ci, vp]
+        L.icar_hip_convection_init.argtypes = [vp, ci, cf, cf, cf, cf, cf, cf, vp, cf]
+        L.icar_hip_cu_nsas.argtypes = [vp, cf, ci, ci, ci, ci]
+        L.icar_hip_nsas_upload.argtypes = [vp, ci, vp]
+        L.icar_hip_nsas_download.argtypes = [vp, ci, vp]
         _lib = L
     return _lib
 

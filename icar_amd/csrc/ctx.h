@@ -54,7 +54,7 @@ struct IcarStepState {
     int landsurface = 0, watersurface = 0, lsm_update_interval = 300;
     float sh_feedback_fraction = 0.625f, lh_feedback_fraction = 1.0f, sfc_layer_thickness = 400.0f;
     double lsm_last_model_time = -999.0;
-    // icar_hip_cu_configure: options%physics%convection (0, ICAR_CU_BMJ or ICAR_CU_TIEDTKE) and options%cu_options with the fractions already inherited
+    // icar_hip_cu_configure: options%physics%convection (0, ICAR_CU_BMJ, ICAR_CU_TIEDTKE or ICAR_CU_NSAS) and options%cu_options with the fractions already inherited
     int convection = 0;
     float cu_tendency_fraction = 1.0f, cu_tend_qv_fraction = 1.0f, cu_tend_qc_fraction = 1.0f, cu_tend_th_fraction = 1.0f, cu_tend_qi_fraction = 1.0f;
 };
@@ -167,6 +167,7 @@ int icar_ysu_sfc_run(icar_hip_ctx *c, float dx);                            // p
 int icar_ysu_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);   // the call of ysu alone (kte the model's)
 int icar_ysu_pbl_run(icar_hip_ctx *c, float dt);                            // pbl(domain, options, dt) for kPBL_YSU on the step's tile
 int icar_ysu_copy(icar_hip_ctx *c, int which, void *host, size_t n, bool to_device);
+const float *icar_ysu_hpbl(const icar_hip_ctx *c);                         // ICAR_YSU_HPBL on the device, or null while YSU is not initialised
 // ra_simple.hip
 int icar_ra_simple_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte, int runlw, int calendar, double D, double year_days);
 int icar_rad_clock(icar_hip_ctx *c, double model_time, double *D, double *year_days);   // day of the year under icar_hip_rad_calendar's anchor
@@ -190,6 +191,10 @@ int icar_cu_tables_copy(icar_hip_ctx *c, float *out, size_t capacity, size_t *n_
 int icar_tiedtke_init_device(icar_hip_ctx *c, const float *znu);           // init_convection for kCU_TIEDTKE: arrays, znu, workspace
 int icar_tiedtke_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);   // CU_TIEDTKE alone (kte the model's)
 int icar_tiedtke_copy(icar_hip_ctx *c, int which, void *host, bool to_device);
+// cu_nsas.hip
+int icar_nsas_init_device(icar_hip_ctx *c, float dx);                      // init_convection for kCU_NSAS: arrays, hpbl, workspace
+int icar_nsas_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);   // cu_nsas alone (kte the model's)
+int icar_nsas_copy(icar_hip_ctx *c, int which, void *host, bool to_device);
 // timestep.hip
 int icar_mp_run(icar_hip_ctx *c, double dt_in, int halo, int subset, bool exner_from_p = false);   // halo / subset < 0: argument not present
 int icar_update_dt(icar_hip_ctx *c, double *seconds);

@@ -1,5 +1,5 @@
 // icar_amd/csrc/cu_bmj.hip -- the convection slot (row C1) on gfx950: convect(domain, options, dt) as it runs for convection = kCU_BMJ
-// (and, around the scheme of cu_tiedtke.hip, for convection = kCU_TIEDTKE: the zeroing and the tendency loop are shared).
+// (and, around the schemes of cu_tiedtke.hip and cu_nsas.hip, for convection = kCU_TIEDTKE and kCU_NSAS: the zeroing and the tendency loop are shared).
 //
 // Reference algorithm: src/physics/cu_driver.f90 -- init_convection :97-253 (XLAND :139-140, lowlyr = 1, bmj_rad_feedback, the call of
 // BMJINIT :230-243), convect :255-514 (the zeroing :272-282, the call of BMJDRV :434-465 on its..ite, jts..jte, kts..kte-1, the
@@ -220,7 +220,7 @@ float *need(icar_hip_ctx *c, int f, const char *who, const char *member)
 CuState *state(icar_hip_ctx *c, const char *who)
 {
     if (c->cu) return c->cu;
-    icar_set_error(std::string(who) + ": the convection slot is not configured (icar_hip_cu_configure with convection = 5, or icar_hip_cu_init)");
+    icar_set_error(std::string(who) + ": the convection slot is not configured (icar_hip_cu_configure with convection = 5, icar_hip_cu_init or icar_hip_convection_init)");
     return nullptr;
 }
 
@@ -272,6 +272,7 @@ void icar_cu_free(icar_hip_ctx *c)
     if (s->ws) hipFree(s->ws);
     if (s->found) hipFree(s->found);
     icar_tiedtke_free(s);
+    icar_nsas_free(s);
     delete s;
     c->cu = nullptr;
 }
@@ -360,8 +361,10 @@ int icar_convect_run(icar_hip_ctx *c, float dt)
     CuState *s = state(c, who);
     if (!s) return 1;
     const icar_hip_step_config &g = st.cfg;
-    const bool tdk = st.convection == ICAR_CU_TIEDTKE;
-    if ((tdk ? icar_tiedtke_levels_ok(c, g.kts, g.kte) : levels_ok(c, s, g.kts, g.kte)) || tile_ok(c, who, g.its, g.ite, g.jts, g.jte)) return 1;
+    const bool tdk = st.convection == ICAR_CU_TIEDTKE, nsas = st.convection == ICAR_CU_NSAS;
+    float *const tend_qc = tdk ? s->tdk[ICAR_TIEDTKE_TEND_QC] : nsas ? s->nsas[ICAR_NSAS_TEND_QC] : nullptr;
+    float *const tend_qi = tdk ? s->tdk[ICAR_TIEDTKE_TEND_QI] : nsas ? s->nsas[ICAR_NSAS_TEND_QI] : nullptr;
+    if ((tdk ? icar_tiedtke_levels_ok(c, g.kts, g.kte) : nsas ? icar_nsas_levels_ok(c, g.kts, g.kte) : levels_ok(c, s, g.kts, g.kte)) || tile_ok(c, who, g.its, g.ite, g.jts, g.jte)) return 1;
     if (g.jte < g.jts) return 0;
     ApplyArgs a;
     const bool on = st.cu_tendency_fraction > 0;                      // :484
@@ -378,11 +381,12 @@ int icar_convect_run(icar_hip_ctx *c, float dt)
     {
         ScopedTimer timer(c, "cu_stream");
         hipLaunchKernelGGL(k_cu_zero, grid, block, 0, c->stream, c->d, g.jts - c->jms, s->arr[ICAR_CU_TEND_TH], s->arr[ICAR_CU_TEND_QV], s->arr[ICAR_CU_RAINCV],
-                           tdk ? s->tdk[ICAR_TIEDTKE_TEND_QC] : nullptr, tdk ? s->tdk[ICAR_TIEDTKE_TEND_QI] : nullptr);
+                           tend_qc, tend_qi);
         HIPCHK(hipGetLastError());
     }
-    if (tdk ? icar_tiedtke_run(c, dt, g.its, g.ite, g.jts, g.jte, g.kts, g.kte) : icar_cu_bmj_run(c, dt, g.its, g.ite, g.jts, g.jte, g.kts, g.kte)) return 1;
-    a.tend_qc = tdk ? s->tdk[ICAR_TIEDTKE_TEND_QC] : nullptr; a.tend_qi = tdk ? s->tdk[ICAR_TIEDTKE_TEND_QI] : nullptr;
+    if (tdk ? icar_tiedtke_run(c, dt, g.its, g.ite, g.jts, g.jte, g.kts, g.kte) : nsas ? icar_nsas_run(c, dt, g.its, g.ite, g.jts, g.jte, g.kts, g.kte)
+            : icar_cu_bmj_run(c, dt, g.its, g.ite, g.jts, g.jte, g.kts, g.kte)) return 1;
+    a.tend_qc = tend_qc; a.tend_qi = tend_qi;
     a.d = c->d; a.j0 = g.jts - c->jms; a.dt = dt;
     a.tend_qv = s->arr[ICAR_CU_TEND_QV]; a.tend_th = s->arr[ICAR_CU_TEND_TH]; a.raincv = s->arr[ICAR_CU_RAINCV];
     a.acc_conv = s->arr[ICAR_CU_ACC_CONV_PCP];

@@ -1,5 +1,5 @@
 // icar_amd/csrc/cu_state.h -- what the convection slot keeps on the device, shared by cu_bmj.hip (the slot's driver and BMJ) and
-// cu_tiedtke.hip (the Tiedtke scheme).
+// cu_tiedtke.hip (the Tiedtke scheme) and cu_nsas.hip (the NSAS scheme).
 #pragma once
 #include "ctx.h"
 
@@ -18,6 +18,14 @@ struct CuState {
     int *tdk_leveltop = nullptr;         // ny: the row's leveltop
     size_t tdk_cols = 0;
     int tdk_levels = 0;                  // levels of the workspace (scheme levels + 2)
+    // NSAS (null until icar_hip_convection_init with convection = 4)
+    float *nsas[ICAR_NSAS_N] = {nullptr};     // tend%qc, tend%qi (nx,nz,ny), PRATEC, HBOT, HTOP, hpbl (nx,ny)
+    float *nsas_ws = nullptr;            // NSAS_NARR x nsas_levels x nsas_cols
+    float *nsas_col = nullptr;           // NSAS_NCOL x nsas_cols: what a column carries from nsas2d to nscv2d
+    int *nsas_limits = nullptr;          // 3 x ny: the row's kbmax, kbm, kmax
+    size_t nsas_cols = 0;
+    int nsas_levels = 0;                 // levels of the workspace (scheme levels + 2)
+    float nsas_dx = 0.0f;                // domain%dx
 };
 
 // cu_bmj.hip
@@ -25,3 +33,6 @@ int icar_cu_common_init(icar_hip_ctx *c);
 // cu_tiedtke.hip
 void icar_tiedtke_free(CuState *s);
 int icar_tiedtke_levels_ok(icar_hip_ctx *c, int kts, int kte);
+// cu_nsas.hip
+void icar_nsas_free(CuState *s);
+int icar_nsas_levels_ok(icar_hip_ctx *c, int kts, int kte);

@@ -47,6 +47,8 @@ struct YsuState {
     int ws_levels = 0;
 };
 
+const float *icar_ysu_hpbl(const icar_hip_ctx *c) { return c->ysu ? c->ysu->arr[ICAR_YSU_HPBL] : nullptr; }
+
 namespace {
 constexpr size_t kWsColumns = (size_t)1 << 17;       // columns per launch of k_ysu_column (a tile row always fits)
 

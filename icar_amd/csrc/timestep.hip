@@ -347,7 +347,8 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
             // (lsm reads u_10m, v_10m and ustar, which are made behind the mass-point winds)
             // (BMJ reads pressure_interface, which the interface kernel writes)
             // (Tiedtke reads w_real as W0AVG: the whole of diagnostic_update precedes convect)
-            const bool wreal_now = stepping && c->step.convection == ICAR_CU_TIEDTKE;
+            // (NSAS likewise)
+            const bool wreal_now = stepping && (c->step.convection == ICAR_CU_TIEDTKE || c->step.convection == ICAR_CU_NSAS);
             face_later = stepping && g.microphysics != 0 && !pbl && !rad && !lsm && !cu;
             if (icar_diagnostic_update_run(c, face_later ? ICAR_DIAG_CELL : 1)) return 1;
             if (stepping && !wreal_now) wreal_later = true;                       // beside the advection, below
@@ -670,7 +671,7 @@ static int cu_configure(const std::string &who, icar_hip_ctx *c, int convection,
 {
     // the values are looked at first: a host learns what is not built without a device
     if (convection == 1) { icar_set_error(who + ": convection = 1 (kCU_TIEDTKE) is not built behind this entry point (it needs znu): icar_hip_cu_init takes it; 0 or 5 (kCU_BMJ)"); return 1; }
-    if (convection == 4) { icar_set_error(who + ": convection = 4 (kCU_NSAS) is not built; 0 or 5 (kCU_BMJ)"); return 1; }
+    if (convection == 4) { icar_set_error(who + ": convection = 4 (kCU_NSAS) is not built behind this entry point (it needs dx): icar_hip_convection_init takes it; 0 or 5 (kCU_BMJ)"); return 1; }
     if (convection == 2) { icar_set_error(who + ": convection = 2 (kCU_SIMPLE): cu_driver.f90 has no branch for it and cu_simple.f90 is not among the reference's objects; 0 or 5 (kCU_BMJ)"); return 1; }
     if (convection == 3) { icar_set_error(who + ": convection = 3 (kCU_KAINFR): its branch in cu_driver.f90 is commented out and cu_kf.f90 is not among the reference's objects; 0 or 5 (kCU_BMJ)"); return 1; }
     if (convection != 0 && convection != ICAR_CU_BMJ) { icar_set_error(who + ": convection is 0 or 5 (kCU_BMJ)"); return 1; }
@@ -699,20 +700,21 @@ int icar_hip_cu_configure(icar_hip_ctx *c, int convection, float stochastic_cu, 
     return cu_configure("cu_configure", c, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction);
 }
 
-int icar_hip_cu_init(icar_hip_ctx *c, int convection, float stochastic_cu, float tendency_fraction, float tend_qv_fraction,
-                     float tend_qc_fraction, float tend_th_fraction, float tend_qi_fraction, const float *znu)
+// icar_hip_cu_init, and icar_hip_convection_init with a convection other than kCU_NSAS (who: the entry point's name in the messages)
+static int cu_init(const std::string &who, icar_hip_ctx *c, int convection, float stochastic_cu, float tendency_fraction, float tend_qv_fraction,
+                   float tend_qc_fraction, float tend_th_fraction, float tend_qi_fraction, const float *znu)
 {
     if (convection != ICAR_CU_TIEDTKE)
-        return cu_configure("cu_init", c, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction);
+        return cu_configure(who, c, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction);
     // the values are looked at first, as in icar_hip_cu_configure
     if (stochastic_cu != ICAR_CU_NO_STOCHASTIC) {
-        icar_set_error("cu_init: stochastic_cu /= kNO_STOCHASTIC (-9999) perturbs W0AVG with random_number (cu_driver.f90:287-295): not built");
+        icar_set_error(who + ": stochastic_cu /= kNO_STOCHASTIC (-9999) perturbs W0AVG with random_number (cu_driver.f90:287-295): not built");
         return 1;
     }
-    if (!(tendency_fraction == tendency_fraction)) { icar_set_error("cu_init: tendency_fraction is NaN"); return 1; }
-    if (!znu) { icar_set_error("cu_init: convection = 1 (kCU_TIEDTKE) needs znu(kms:kme)"); return 1; }
-    if (!c) { icar_set_error("cu_init: null ctx"); return 1; }
-    for (int k = 0; k < c->d.nz; ++k) if (!(znu[k] == znu[k])) { icar_set_error("cu_init: znu holds a NaN"); return 1; }
+    if (!(tendency_fraction == tendency_fraction)) { icar_set_error(who + ": tendency_fraction is NaN"); return 1; }
+    if (!znu) { icar_set_error(who + ": convection = 1 (kCU_TIEDTKE) needs znu(kms:kme)"); return 1; }
+    if (!c) { icar_set_error(who + ": null ctx"); return 1; }
+    for (int k = 0; k < c->d.nz; ++k) if (!(znu[k] == znu[k])) { icar_set_error(who + ": znu holds a NaN"); return 1; }
     HIPCHK(hipSetDevice(c->device));
     if (icar_tiedtke_init_device(c, znu)) return 1;
     IcarStepState &s = c->step;
@@ -723,6 +725,12 @@ int icar_hip_cu_init(icar_hip_ctx *c, int convection, float stochastic_cu, float
     s.cu_tend_qi_fraction = tend_qi_fraction < 0 ? tendency_fraction : tend_qi_fraction;
     s.convection = convection;
     return 0;
+}
+
+int icar_hip_cu_init(icar_hip_ctx *c, int convection, float stochastic_cu, float tendency_fraction, float tend_qv_fraction,
+                     float tend_qc_fraction, float tend_th_fraction, float tend_qi_fraction, const float *znu)
+{
+    return cu_init("cu_init", c, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction, znu);
 }
 
 int icar_hip_cu_tiedtke(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte)
@@ -742,6 +750,54 @@ int icar_hip_tiedtke_download(icar_hip_ctx *c, int which, void *host)
 {
     if (icar_enter(c, "tiedtke_download", host != nullptr)) return 1;
     return icar_tiedtke_copy(c, which, host, false);
+}
+
+// init_convection with every scheme that is built (cu_driver.f90:97-253)
+int icar_hip_convection_init(icar_hip_ctx *c, int convection, float stochastic_cu, float tendency_fraction, float tend_qv_fraction,
+                             float tend_qc_fraction, float tend_th_fraction, float tend_qi_fraction, const float *znu, float dx)
+{
+    if (convection != ICAR_CU_NSAS)
+        return cu_init("convection_init", c, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction, znu);
+    // the values are looked at first, as in icar_hip_cu_configure
+    if (stochastic_cu != ICAR_CU_NO_STOCHASTIC) {
+        icar_set_error("convection_init: stochastic_cu /= kNO_STOCHASTIC (-9999) perturbs W0AVG with random_number (cu_driver.f90:287-295): not built");
+        return 1;
+    }
+    if (!(tendency_fraction == tendency_fraction)) { icar_set_error("convection_init: tendency_fraction is NaN"); return 1; }
+    if (!(dx > 0.0f) || dx > 3.0e38f) {
+        icar_set_error("convection_init: convection = 4 (kCU_NSAS) needs domain%dx > 0 (dx_factor = 250. / delx, cu_nsas.f90:568; dx_factor_nsas, cu_driver.f90:357-361)");
+        return 1;
+    }
+    if (!c) { icar_set_error("convection_init: null ctx"); return 1; }
+    HIPCHK(hipSetDevice(c->device));
+    if (icar_nsas_init_device(c, dx)) return 1;
+    IcarStepState &s = c->step;
+    s.cu_tendency_fraction = tendency_fraction;
+    s.cu_tend_qv_fraction = tend_qv_fraction < 0 ? tendency_fraction : tend_qv_fraction;      // options_obj.f90:1646-1649
+    s.cu_tend_qc_fraction = tend_qc_fraction < 0 ? tendency_fraction : tend_qc_fraction;
+    s.cu_tend_th_fraction = tend_th_fraction < 0 ? tendency_fraction : tend_th_fraction;
+    s.cu_tend_qi_fraction = tend_qi_fraction < 0 ? tendency_fraction : tend_qi_fraction;
+    s.convection = convection;
+    return 0;
+}
+
+int icar_hip_cu_nsas(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte)
+{
+    if (icar_enter(c, "cu_nsas")) return 1;
+    const bool cfg = c->step.configured;
+    return icar_nsas_run(c, dt, its, ite, jts, jte, cfg ? c->step.cfg.kts : c->kms, cfg ? c->step.cfg.kte : c->kme);
+}
+
+int icar_hip_nsas_upload(icar_hip_ctx *c, int which, const void *host)
+{
+    if (icar_enter(c, "nsas_upload", host != nullptr)) return 1;
+    return icar_nsas_copy(c, which, const_cast<void *>(host), true);
+}
+
+int icar_hip_nsas_download(icar_hip_ctx *c, int which, void *host)
+{
+    if (icar_enter(c, "nsas_download", host != nullptr)) return 1;
+    return icar_nsas_copy(c, which, host, false);
 }
 
 int icar_hip_cu_bmj(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte)

@@ -93,8 +93,9 @@ class domain_t:
         ckey = (0,) if cu == 0 or co is None else (cu, float(co.stochastic_cu), float(co.tendency_fraction)) + tuple(float(f) for f in co.resolved())
         if cu != 0 and co is None: ckey = (cu, -9999.0, 1.0, 1.0, 1.0, 1.0, 1.0)
         if ckey != self._cu_key:
-            from .convection import cu_configure, cu_init
+            from .convection import cu_configure, cu_init, convection_init
             if cu == 1: cu_init(self, *ckey)      # kCU_TIEDTKE needs znu: icar_hip_cu_init
+            elif cu == 4: convection_init(self, *ckey)      # kCU_NSAS needs dx: icar_hip_convection_init
             else: cu_configure(self, *ckey)
         adv = options.physics.advection if advection is None else advection
         adv_ids = tuple(KVARS[n][0] for n in ADVECTION_ORDER if options.vars_to_advect.get(n, 0) > 0)

@@ -30,6 +30,8 @@ module icar_hip
             hip_cu_configure, hip_cu_bmj, hip_convect, hip_cu_reset, hip_cu_upload, hip_cu_download, ICAR_CU_BMJ, ICAR_CU_NO_STOCHASTIC, &
             hip_cu_init, hip_cu_tiedtke, hip_tiedtke_upload, hip_tiedtke_download, hip_tiedtke_download_ktype, ICAR_CU_TIEDTKE, &
             ICAR_TIEDTKE_TEND_QC, ICAR_TIEDTKE_TEND_QI, ICAR_TIEDTKE_PRATEC, ICAR_TIEDTKE_KTYPE, ICAR_TIEDTKE_N, &
+            hip_convection_init, hip_cu_nsas, hip_nsas_upload, hip_nsas_download, ICAR_CU_NSAS, &
+            ICAR_NSAS_TEND_QC, ICAR_NSAS_TEND_QI, ICAR_NSAS_PRATEC, ICAR_NSAS_HBOT, ICAR_NSAS_HTOP, ICAR_NSAS_HPBL, ICAR_NSAS_N, &
             ICAR_CU_CLDEFI, ICAR_CU_ACC_CONV_PCP, ICAR_CU_RAINCV, ICAR_CU_CUTOP, ICAR_CU_CUBOT, ICAR_CU_TEND_TH, ICAR_CU_TEND_QV, ICAR_CU_N, &
             ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_SELF, ICAR_N_ADVECTABLE
   public :: ICAR_F_WATER_VAPOR, ICAR_F_CLOUD_WATER, ICAR_F_RAIN, ICAR_F_SNOW, ICAR_F_POTENTIAL_TEMPERATURE, &
@@ -75,6 +77,10 @@ module icar_hip
   integer(c_int), parameter :: ICAR_CU_TIEDTKE = 1      ! kCU_TIEDTKE, icar_constants.f90
   ! enum icar_hip_tiedtke_array: the Tiedtke scheme's own arrays: tend%qc, tend%qi (nx,nz,ny), PRATEC (nx,ny) REAL(4), KTYPE (nx,ny) INTEGER(4)
   integer(c_int), parameter :: ICAR_TIEDTKE_TEND_QC=0, ICAR_TIEDTKE_TEND_QI=1, ICAR_TIEDTKE_PRATEC=2, ICAR_TIEDTKE_KTYPE=3, ICAR_TIEDTKE_N=4
+  integer(c_int), parameter :: ICAR_CU_NSAS = 4         ! kCU_NSAS, icar_constants.f90
+  ! enum icar_hip_nsas_array: the NSAS scheme's own REAL(4) arrays: tend%qc, tend%qi (nx,nz,ny), PRATEC, HBOT, HTOP, hpbl (nx,ny)
+  integer(c_int), parameter :: ICAR_NSAS_TEND_QC=0, ICAR_NSAS_TEND_QI=1, ICAR_NSAS_PRATEC=2, ICAR_NSAS_HBOT=3, ICAR_NSAS_HTOP=4, ICAR_NSAS_HPBL=5, &
+                               ICAR_NSAS_N=6
 
   !> struct icar_hip_step_config == the members of options_t / grid_t the sub-step loop reads (time_step.f90:440-551)
   type, bind(C) :: hip_step_config_t
@@ -255,6 +261,20 @@ module icar_hip
        import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
      end function
      integer(c_int) function icar_hip_tiedtke_download(ctx, which, host) bind(C, name="icar_hip_tiedtke_download")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
+     end function
+     integer(c_int) function icar_hip_convection_init(ctx, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, &
+                                                      tend_th_fraction, tend_qi_fraction, znu, dx) bind(C, name="icar_hip_convection_init")
+       import; type(c_ptr), value :: ctx, znu; integer(c_int), value :: convection
+       real(c_float), value :: stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction, dx
+     end function
+     integer(c_int) function icar_hip_cu_nsas(ctx, dt, its, ite, jts, jte) bind(C, name="icar_hip_cu_nsas")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: dt; integer(c_int), value :: its, ite, jts, jte
+     end function
+     integer(c_int) function icar_hip_nsas_upload(ctx, which, host) bind(C, name="icar_hip_nsas_upload")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
+     end function
+     integer(c_int) function icar_hip_nsas_download(ctx, which, host) bind(C, name="icar_hip_nsas_download")
        import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
      end function
      integer(c_int) function icar_hip_wsm6_init(ctx) bind(C, name="icar_hip_wsm6_init")
@@ -629,7 +649,7 @@ contains
     nz = int(n)
   end function
 
-  !> init_convection (cu_driver.f90:97-253): options%physics%convection (0 or ICAR_CU_BMJ; Tiedtke goes through hip_cu_init, NSAS is not built, 2 and 3 have no
+  !> init_convection (cu_driver.f90:97-253): options%physics%convection (0 or ICAR_CU_BMJ; Tiedtke goes through hip_cu_init, NSAS through hip_convection_init, 2 and 3 have no
   !! branch in the reference) and options%cu_options (stochastic_cu must be kNO_STOCHASTIC; a negative fraction inherits tendency_fraction)
   subroutine hip_cu_configure(ctx, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction)
     type(hip_ctx_t), intent(in) :: ctx
@@ -715,6 +735,41 @@ contains
     type(hip_ctx_t), intent(in) :: ctx
     integer(c_int), intent(inout), target, contiguous :: a(:,:)
     call check(icar_hip_tiedtke_download(ctx%p, ICAR_TIEDTKE_KTYPE, c_loc(a)), "tiedtke_download")
+  end subroutine
+
+  !> init_convection with every scheme that is built: 0, ICAR_CU_BMJ and ICAR_CU_TIEDTKE as hip_cu_init; ICAR_CU_NSAS takes domain%dx
+  subroutine hip_convection_init(ctx, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, &
+                                 tend_qi_fraction, znu, dx)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer, intent(in) :: convection
+    real, intent(in) :: stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, tend_th_fraction, tend_qi_fraction, dx
+    real(c_float), intent(in), target, contiguous :: znu(:)
+    call check(icar_hip_convection_init(ctx%p, int(convection,c_int), real(stochastic_cu,c_float), real(tendency_fraction,c_float), &
+                                        real(tend_qv_fraction,c_float), real(tend_qc_fraction,c_float), real(tend_th_fraction,c_float), &
+                                        real(tend_qi_fraction,c_float), c_loc(znu), real(dx,c_float)), "convection_init")
+  end subroutine
+
+  !> the call of cu_nsas alone (cu_driver.f90:363-417) on a range of columns
+  subroutine hip_cu_nsas(ctx, dt, its, ite, jts, jte)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: dt
+    integer, intent(in) :: its, ite, jts, jte
+    call check(icar_hip_cu_nsas(ctx%p, real(dt,c_float), int(its,c_int), int(ite,c_int), int(jts,c_int), int(jte,c_int)), "cu_nsas")
+  end subroutine
+
+  !> the NSAS scheme's REAL(4) arrays by ICAR_NSAS_*: (nx,nz,ny) for the two tendencies, (nx,ny) for PRATEC, HBOT, HTOP and hpbl
+  subroutine hip_nsas_upload(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(in), target, contiguous :: a(..)
+    call check(icar_hip_nsas_upload(ctx%p, which, c_loc(a)), "nsas_upload")
+  end subroutine
+
+  subroutine hip_nsas_download(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(inout), target, contiguous :: a(..)
+    call check(icar_hip_nsas_download(ctx%p, which, c_loc(a)), "nsas_download")
   end subroutine
 
   subroutine hip_mp_reset(ctx)

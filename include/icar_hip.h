@@ -386,7 +386,8 @@ int icar_hip_lsm_layers(icar_hip_ctx *ctx, int *nz);
 /* ---- C1: the convection slot (src/physics/cu_driver.f90 with convection = kCU_BMJ, src/physics/cu_bmj.f90) ---------------------------
  * icar_hip_cu_configure: init_convection (cu_driver.f90:97-253) -- options%physics%convection and options%cu_options.
  *     convection: 0 (convect returns at once, :264) or ICAR_CU_BMJ = kCU_BMJ (icar_constants.f90:345).  1 (kCU_TIEDTKE) is refused here:
- *     it needs znu, which icar_hip_cu_init (C2) takes.  4 (kCU_NSAS) is refused: not built.  2 (kCU_SIMPLE) is refused: cu_driver.f90 has no branch for it and cu_simple.f90 is not among the
+ *     it needs znu, which icar_hip_cu_init (C2) takes.  4 (kCU_NSAS) is refused here ("not built" behind this entry point): it needs dx,
+ *     which icar_hip_convection_init (C3) takes.  2 (kCU_SIMPLE) is refused: cu_driver.f90 has no branch for it and cu_simple.f90 is not among the
  *     reference's objects; 3 (kCU_KAINFR) likewise: its branch in cu_driver.f90 is commented out and cu_kf.f90 is not built.
  *     stochastic_cu: ICAR_CU_NO_STOCHASTIC = kNO_STOCHASTIC (-9999); anything else draws from random_number in the reference
  *     (:287-295) and is refused.  tendency_fraction (default 1.0) and the four fractions of qv, qc, th, qi (negative = inherit
@@ -475,6 +476,48 @@ int icar_hip_cu_init(icar_hip_ctx *ctx, int convection, float stochastic_cu, flo
 int icar_hip_cu_tiedtke(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, int jte);
 int icar_hip_tiedtke_upload(icar_hip_ctx *ctx, int which, const void *host);
 int icar_hip_tiedtke_download(icar_hip_ctx *ctx, int which, void *host);
+
+/* ---- C3: the NSAS scheme in the convection slot (cu_driver.f90 with convection = kCU_NSAS, src/physics/cu_nsas.f90) -------------------
+ * icar_hip_convection_init == init_convection(domain, options) (cu_driver.f90:97-253) with every scheme that is built.  convection 0,
+ *     ICAR_CU_BMJ and ICAR_CU_TIEDTKE: exactly icar_hip_cu_init (dx ignored).  ICAR_CU_NSAS = kCU_NSAS (icar_constants.f90; :59-73,
+ *     :173-202): dx is domain%dx, kept (it decides dx_factor_nsas, :357-361, and is nsas2d's delx); a dx <= 0 or a dx that is not a
+ *     number is refused, the values being looked at before the context.  The call allocates tend%qc, tend%qi (zero as nsasinit leaves
+ *     them, cu_nsas.f90:2155-2186), PRATEC, HBOT, HTOP and hpbl (ICAR_NSAS_*), the slot's ICAR_CU_* arrays and the column workspace:
+ *     36 arrays x (min(kme - kms, 128) + 2) levels x min(nx ny, 32768) columns of REAL(4), and 5 values per column beside it.  hpbl
+ *     is filled with 1000 unless the context's boundary layer is ICAR_PBL_YSU at that moment (:180-186).
+ * icar_hip_cu_nsas == the call of cu_nsas (:363-417) alone on its..ite, jts..jte and the levels kts..kte-1 of icar_hip_step_configure
+ *     (kms..kme-1 without one), with itimestep = STEPCU = 1, mp_physics = 5 (ncloud = 2), pgcon absent (0.55) and the driver's
+ *     constants: from TEMPERATURE (as diagnostic_update left it), WATER_VAPOR, CLOUD_WATER, CLOUD_ICE, EXNER, DENSITY, W_REAL (W0AVG
+ *     without the stochastic term), DZ_INTERFACE, PRESSURE, PRESSURE_INTERFACE, U_MASS, V_MASS (they set the downdraft's edt),
+ *     SENSIBLE_HEAT, LATENT_HEAT (qfx = latent_heat / 2260000), LAND_MASK (never uploaded = all land; XLAND = 2 where the mask is 0 or
+ *     2) and hpbl -- ICAR_YSU_HPBL once YSU is initialised (pbl precedes convect in the sub-step), ICAR_NSAS_HPBL otherwise --
+ *     -> ICAR_CU_TEND_TH, ICAR_CU_TEND_QV, ICAR_NSAS_TEND_QC, ICAR_NSAS_TEND_QI, ICAR_CU_RAINCV (the deep and the shallow rain),
+ *     ICAR_NSAS_PRATEC, ICAR_NSAS_HBOT, ICAR_NSAS_HTOP of those columns; nothing else is touched.  Bit-identical to the compiled
+ *     reference.  nsas2d's kbmax, kbm and kmax are made per row from ALL columns its..ite of the row (cu_nsas.f90:619-632): over
+ *     terrain a column's result depends on which columns share its row and tile, so an N-image run may differ from the one-image run,
+ *     in the reference and here.  tend%u / tend%v are not built: convect applies neither (:502-507 is commented out), and nothing
+ *     evaluated reads the updated winds (icar_amd/csrc/nsas_column.h has the derivation).  Levels: kts = 1, at least 3 levels
+ *     kts..kte (with one scheme level the reference reads xlamue(i,0), cu_nsas.f90:2456), at most 129; all refused before any launch.
+ * icar_hip_convect / _substep / _step / _step_n run this scheme when icar_hip_convection_init selected it: the four tendencies and
+ *     RAINCV are zeroed, the scheme runs, the four are applied with their fractions and RAINCV is added to the two precipitation
+ *     sums; the whole of diagnostic_update, w_real included, precedes convect in the sub-step.
+ * icar_hip_nsas_upload / _download: the scheme's own arrays by ICAR_NSAS_*, REAL(4): the two tendencies (nx,nz,ny), the rest (nx,ny).
+ *     hpbl is a restart variable and may be uploaded. */
+enum { ICAR_CU_NSAS = 4 };
+enum icar_hip_nsas_array {
+    ICAR_NSAS_TEND_QC = 0,         /* domain%tend%qc (nx,nz,ny)                                                   */
+    ICAR_NSAS_TEND_QI = 1,         /* domain%tend%qi (nx,nz,ny)                                                   */
+    ICAR_NSAS_PRATEC = 2,          /* cu_driver.f90's PRATEC of the last call (mm/s)                              */
+    ICAR_NSAS_HBOT = 3,            /* lowest_convection_layer, highest_convection_layer of the last call          */
+    ICAR_NSAS_HTOP = 4,            /*   (level indices as REAL(4); kte and 0 without convection)                  */
+    ICAR_NSAS_HPBL = 5,            /* domain%hpbl%data_2d as init_convection left it (read while YSU is not initialised) */
+    ICAR_NSAS_N = 6
+};
+int icar_hip_convection_init(icar_hip_ctx *ctx, int convection, float stochastic_cu, float tendency_fraction, float tend_qv_fraction,
+                             float tend_qc_fraction, float tend_th_fraction, float tend_qi_fraction, const float *znu, float dx);
+int icar_hip_cu_nsas(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, int jte);
+int icar_hip_nsas_upload(icar_hip_ctx *ctx, int which, const void *host);
+int icar_hip_nsas_download(icar_hip_ctx *ctx, int which, void *host);
 
 /* ---- T2: CFL reduction for compute_dt (src/main/time_step.f90:217-330, cfl_strictness 3) -----
  * out = max over the tile of max(|u_i|,|u_i+1|)/dx + max(|v_j|,|v_j+1|)/dx + max(|w_k|,|w_k-1|)/dz_levels(k) */
