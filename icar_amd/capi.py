@@ -37,6 +37,8 @@ SYMBOLS = [
     "icar_hip_cu_configure", "icar_hip_cu_bmj", "icar_hip_convect", "icar_hip_cu_reset", "icar_hip_cu_upload", "icar_hip_cu_download", "icar_hip_cu_tables",
     "icar_hip_cu_init", "icar_hip_cu_tiedtke", "icar_hip_tiedtke_upload", "icar_hip_tiedtke_download",
     "icar_hip_convection_init", "icar_hip_cu_nsas", "icar_hip_nsas_upload", "icar_hip_nsas_download",
+    "icar_hip_forcing_configure", "icar_hip_forcing_upload", "icar_hip_forcing_download", "icar_hip_interpolate_forcing",
+    "icar_hip_update_delta_fields", "icar_hip_forcing_step",
 ]
 
 
@@ -49,6 +51,12 @@ class lt_options_c(ctypes.Structure):          # struct icar_hip_lt_options (inc
                 ("nsqmax", ctypes.c_float), ("nsqmin", ctypes.c_float),
                 ("n_dir_values", ctypes.c_int), ("n_nsq_values", ctypes.c_int), ("n_spd_values", ctypes.c_int),
                 ("minimum_layer_size", ctypes.c_float)]
+
+
+class forcing_geo_c(ctypes.Structure):         # struct icar_hip_forcing_geo (include/icar_hip.h)
+    _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("w", ctypes.c_void_p), ("z", ctypes.c_void_p), ("zw", ctypes.c_void_p),
+                ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("nx_f", ctypes.c_int), ("nz_f", ctypes.c_int), ("ny_f", ctypes.c_int),
+                ("i0", ctypes.c_int), ("j0", ctypes.c_int)]
 
 
 N_ADVECTABLE = 11
@@ -139,6 +147,13 @@ def lib():
         L.icar_hip_cu_nsas.argtypes = [vp, cf, ci, ci, ci, ci]
         L.icar_hip_nsas_upload.argtypes = [vp, ci, vp]
         L.icar_hip_nsas_download.argtypes = [vp, ci, vp]
+        gp = ctypes.POINTER(forcing_geo_c)
+        L.icar_hip_forcing_configure.argtypes = [vp, gp, gp, gp, ci, vp, vp, ci]
+        L.icar_hip_forcing_upload.argtypes = [vp, ci, vp, ci, ci, ci]
+        L.icar_hip_forcing_download.argtypes = [vp, ci, vp, ctypes.c_size_t]
+        L.icar_hip_interpolate_forcing.argtypes = [vp, ctypes.POINTER(ci), ci, ci, ci, ci]
+        L.icar_hip_update_delta_fields.argtypes = [vp, ctypes.POINTER(ci), ci, cd]
+        L.icar_hip_forcing_step.argtypes = [vp, ctypes.POINTER(ci), ci, ci, ci, ci, ci, cf, ci, cd]
         _lib = L
     return _lib
 

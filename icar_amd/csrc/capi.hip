@@ -26,9 +26,8 @@ int icar_enter(icar_hip_ctx *c, const char *who, bool pointers_ok)
 // ------------------------------------------------------------------------------------------------
 // field registry
 // ------------------------------------------------------------------------------------------------
-static bool field_is_2dd(int f) { return f == ICAR_F_PRECIPITATION || f == ICAR_F_SNOWFALL || f == ICAR_F_GRAUPEL_ACC || f == ICAR_F_SINTHETA || f == ICAR_F_COSTHETA; }
-// a field the Courant winds are made of: rewriting it makes them, and a prefetched CFL maximum, stale (icar_winds_changed)
-static bool field_feeds_winds(int f) { return f == ICAR_F_U || f == ICAR_F_V || f == ICAR_F_W || (f >= ICAR_F_DENSITY && f <= ICAR_F_ADVECTION_DZ); }
+static bool field_is_2dd(int f) { return icar_field_is_2dd(f); }                   // (ctx.h has the definitions)
+static bool field_feeds_winds(int f) { return icar_field_feeds_winds(f); }
 
 size_t icar_field_count(const icar_hip_ctx *c, int f)
 {
@@ -158,6 +157,7 @@ int icar_hip_ctx_destroy(icar_hip_ctx *c)
     icar_wsm6_free(c);
     icar_thompson_free(c);
     icar_linwinds_free(c);
+    icar_forcing_free(c);
     icar_comm_free(c);
     if (c->step.h_val) hipHostFree(c->step.h_val);
     if (c->on_aux) c->stream = c->main_saved;

@@ -28,6 +28,7 @@ struct Wsm6State;        // mp_wsm6.hip
 struct IcarComm;         // comm.hip
 struct CuState;          // cu_bmj.hip
 struct YsuState;         // pbl_ysu.hip
+struct ForcingState;     // forcing.hip
 
 // state of the step driver (timestep.hip): the options / grid members the sub-step loop reads, the model clock, and what
 // mp_driver.f90 keeps in SAVE variables (last_model_time)
@@ -120,6 +121,7 @@ struct icar_hip_ctx {
     Wsm3State *wsm3 = nullptr;
     Wsm6State *wsm6 = nullptr;
     IcarComm *comm = nullptr;            // halo transport + co_min (comm.hip)
+    ForcingState *forcing = nullptr;     // forcing.hip: the look-up tables, the forcing's own arrays, the temporaries of interpolate_forcing
     IcarStepState step;                  // timestep.hip
     // timing
     bool timing = false;
@@ -136,6 +138,12 @@ int icar_hip_check(hipError_t e, const char *what);
 // field geometry
 size_t icar_field_count(const icar_hip_ctx *c, int field);
 float *icar_field_f(icar_hip_ctx *c, int field, bool required = true);   // allocates lazily
+// the registry's classes of field ids, one definition for every file that asks
+inline bool icar_field_is_2dd(int f) { return f == ICAR_F_PRECIPITATION || f == ICAR_F_SNOWFALL || f == ICAR_F_GRAUPEL_ACC || f == ICAR_F_SINTHETA || f == ICAR_F_COSTHETA; }
+// a field the Courant winds are made of: rewriting it makes them, and a prefetched CFL maximum, stale (icar_winds_changed)
+inline bool icar_field_feeds_winds(int f) { return f == ICAR_F_U || f == ICAR_F_V || f == ICAR_F_W || (f >= ICAR_F_DENSITY && f <= ICAR_F_ADVECTION_DZ); }
+// a REAL(4) field with levels: (nx, nz, ny), u's (nx+1, nz, ny) or v's (nx, nz, ny+1) -- what a dqdt_3d mirror can belong to
+inline bool icar_field_is_3d(const icar_hip_ctx *c, int f) { return f >= 0 && f < ICAR_N_FIELD_SLOTS && !icar_field_is_2dd(f) && icar_field_count(c, f) >= c->n3; }
 
 // timing helpers
 struct ScopedTimer {
@@ -249,3 +257,10 @@ int icar_linwinds_lut_entry(icar_hip_ctx *c, int comp, int k, int i, int j, floa
 int icar_linwinds_pert_copy(icar_hip_ctx *c, int comp, float *host, int to_dev);
 int icar_linwinds_terrain_frequency(icar_hip_ctx *c, double *out, size_t cap, int *fnx, int *fny);
 int icar_spatial_winds_run(icar_hip_ctx *c, int update);
+// ... its smooth_array_3d (ydim = 3) pair, which forcing.hip launches on the forcing's u / v too: in (nx, nz, ny) -> row means -> out
+__global__ void k_lw_rowmeans(Dims d, int w, const float *__restrict__ in, double *__restrict__ rowmeans);
+__global__ void k_lw_colsmooth(Dims d, int w, const double *__restrict__ rowmeans, float *__restrict__ out);
+// forcing.hip
+void icar_forcing_free(icar_hip_ctx *c);
+int icar_interpolate_forcing_run(icar_hip_ctx *c, const int *fields, int n, int pressure_field, int theta_field, int update);
+int icar_update_delta_fields_run(icar_hip_ctx *c, const int *fields, int n, double dt);

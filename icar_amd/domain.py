@@ -200,6 +200,16 @@ class domain_t:
         check(lib().icar_hip_apply_forcing(self.ctx, ctypes.c_double(dt_seconds), ids, fb, len(forced), int(g.west_boundary),
                                            int(g.east_boundary), int(g.south_boundary), int(g.north_boundary)), "apply_forcing")
 
+    def interpolate_forcing(self, forcing, update=False, **kw):
+        """domain%interpolate_forcing(forcing, update) (domain_obj.f90:2559-2643) on the device (icar_amd.forcing)."""
+        from .forcing import interpolate_forcing
+        interpolate_forcing(self, forcing, update, **kw)
+
+    def update_delta_fields(self, dt_seconds, names=None):
+        """domain%update_delta_fields(dt) (domain_obj.f90:2339-2372): dqdt_3d = (dqdt_3d - data_3d) / dt for the forced variables and w."""
+        from .forcing import update_delta_fields
+        update_delta_fields(self, dt_seconds, names)
+
     def enforce_limits(self, names):
         """domain%enforce_limits (domain_obj.f90:2228-2243): clamp negatives to zero."""
         ids = (ctypes.c_int * len(names))(*[self.fid(n) for n in names])

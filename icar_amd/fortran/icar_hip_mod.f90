@@ -31,6 +31,7 @@ module icar_hip
             hip_cu_init, hip_cu_tiedtke, hip_tiedtke_upload, hip_tiedtke_download, hip_tiedtke_download_ktype, ICAR_CU_TIEDTKE, &
             ICAR_TIEDTKE_TEND_QC, ICAR_TIEDTKE_TEND_QI, ICAR_TIEDTKE_PRATEC, ICAR_TIEDTKE_KTYPE, ICAR_TIEDTKE_N, &
             hip_convection_init, hip_cu_nsas, hip_nsas_upload, hip_nsas_download, ICAR_CU_NSAS, &
+            hip_forcing_geo_t, hip_forcing_configure, hip_forcing_upload, hip_interpolate_forcing, hip_update_delta_fields, hip_forcing_step, &
             ICAR_NSAS_TEND_QC, ICAR_NSAS_TEND_QI, ICAR_NSAS_PRATEC, ICAR_NSAS_HBOT, ICAR_NSAS_HTOP, ICAR_NSAS_HPBL, ICAR_NSAS_N, &
             ICAR_CU_CLDEFI, ICAR_CU_ACC_CONV_PCP, ICAR_CU_RAINCV, ICAR_CU_CUTOP, ICAR_CU_CUBOT, ICAR_CU_TEND_TH, ICAR_CU_TEND_QV, ICAR_CU_N, &
             ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_SELF, ICAR_N_ADVECTABLE
@@ -44,6 +45,19 @@ module icar_hip
             ICAR_F_TERRAIN, ICAR_F_LAND_MASK, ICAR_F_LATITUDE, ICAR_F_LONGITUDE, ICAR_F_SHORTWAVE, ICAR_F_LONGWAVE, ICAR_F_CLOUD_FRACTION, &
             ICAR_F_ROUGHNESS_Z0, ICAR_F_U_10M, ICAR_F_V_10M, ICAR_F_USTAR, ICAR_F_SST, ICAR_F_SKIN_TEMPERATURE, ICAR_F_SENSIBLE_HEAT, &
             ICAR_F_LATENT_HEAT, ICAR_F_QSFC, ICAR_F_QFX, ICAR_F_DZ_INTERFACE
+
+  ! struct icar_hip_forcing_geo (include/icar_hip.h) and what a host fills in: pointers to the reference's own look-up tables
+  ! (forcing%geo%geolut%x / %y / %w, forcing%geo%vert_lut%z / %w; for u / v those of forcing%geo_u / %geo_v on the extended grids)
+  type, bind(C) :: forcing_geo_c
+     type(c_ptr) :: x, y, w, z, zw
+     integer(c_int) :: nx, ny, nx_f, nz_f, ny_f, i0, j0
+  end type
+  type hip_forcing_geo_t
+     integer(c_int), pointer, contiguous :: x(:,:,:) => null(), y(:,:,:) => null(), z(:,:,:,:) => null()
+     real(c_float), pointer, contiguous :: w(:,:,:) => null(), zw(:,:,:,:) => null()
+     integer :: nx_f = 0, nz_f = 0, ny_f = 0      ! extents of the forcing variables these tables index
+     integer :: i0 = 0, j0 = 0                    ! u, v: u_grid%ims - u_grid2d_ext%ims, u_grid%jms - u_grid2d_ext%jms (likewise v)
+  end type
 
   ! enum icar_hip_field (include/icar_hip.h)
   integer(c_int), parameter :: ICAR_F_WATER_VAPOR=0, ICAR_F_CLOUD_WATER=1, ICAR_F_RAIN=2, ICAR_F_SNOW=3, &
@@ -382,6 +396,26 @@ module icar_hip
      end function
      integer(c_int) function icar_hip_co_min(ctx, v) bind(C, name="icar_hip_co_min")
        import; type(c_ptr), value :: ctx; real(c_double), intent(inout) :: v
+     end function
+     integer(c_int) function icar_hip_forcing_configure(ctx, mass, u, v, nsmooth, forcing_z, domain_z, time_varying_z) bind(C, name="icar_hip_forcing_configure")
+       import; type(c_ptr), value :: ctx, mass, u, v, forcing_z, domain_z; integer(c_int), value :: nsmooth, time_varying_z
+     end function
+     integer(c_int) function icar_hip_forcing_upload(ctx, field, lo, nx_f, nz_f, ny_f) bind(C, name="icar_hip_forcing_upload")
+       import; type(c_ptr), value :: ctx, lo; integer(c_int), value :: field, nx_f, nz_f, ny_f
+     end function
+     integer(c_int) function icar_hip_forcing_download(ctx, field, lo, count) bind(C, name="icar_hip_forcing_download")
+       import; type(c_ptr), value :: ctx, lo; integer(c_int), value :: field; integer(c_size_t), value :: count
+     end function
+     integer(c_int) function icar_hip_interpolate_forcing(ctx, fields, n, pressure_field, theta_field, update) bind(C, name="icar_hip_interpolate_forcing")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: n, pressure_field, theta_field, update; integer(c_int), intent(in) :: fields(*)
+     end function
+     integer(c_int) function icar_hip_update_delta_fields(ctx, fields, n, dt_seconds) bind(C, name="icar_hip_update_delta_fields")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: n; integer(c_int), intent(in) :: fields(*); real(c_double), value :: dt_seconds
+     end function
+     integer(c_int) function icar_hip_forcing_step(ctx, fields, n, pressure_field, theta_field, windtype, wind_iterations, dx, halo, dt_seconds) &
+                                                   bind(C, name="icar_hip_forcing_step")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: n, pressure_field, theta_field, windtype, wind_iterations, halo
+       integer(c_int), intent(in) :: fields(*); real(c_float), value :: dx; real(c_double), value :: dt_seconds
      end function
      integer(c_int) function icar_hip_update_winds(ctx, windtype, wind_iterations, dx, halo, update) bind(C, name="icar_hip_update_winds")
        import; type(c_ptr), value :: ctx; integer(c_int), value :: windtype, wind_iterations, halo, update; real(c_float), value :: dx
@@ -1106,6 +1140,71 @@ contains
   subroutine hip_diagnostic_update(ctx)
     type(hip_ctx_t), intent(in) :: ctx
     call check(icar_hip_diagnostic_update(ctx%p), "diagnostic_update")
+  end subroutine
+
+  !> the look-up tables of forcing%geo / %geo_u / %geo_v, domain%nsmooth and, for adjust_pressure, forcing%geo%z with domain%geo%z:
+  !! once, behind the reference's geo_LUT / vLUT (init time).  Every index is validated before anything is stored.
+  subroutine hip_forcing_configure(ctx, mass, nsmooth, u, v, forcing_z, domain_z, time_varying_z)
+    type(hip_ctx_t), intent(in) :: ctx
+    type(hip_forcing_geo_t), intent(in), target :: mass
+    integer, intent(in) :: nsmooth
+    type(hip_forcing_geo_t), intent(in), target, optional :: u, v
+    real(c_float), intent(in), target, contiguous, optional :: forcing_z(:,:,:), domain_z(:,:,:)
+    logical, intent(in), optional :: time_varying_z
+    type(forcing_geo_c), target :: cm, cu, cv
+    type(c_ptr) :: pu, pv, pzf, pzd
+    integer(c_int) :: tvz
+    cm = as_c(mass); pu = c_null_ptr; pv = c_null_ptr; pzf = c_null_ptr; pzd = c_null_ptr; tvz = 0
+    if (present(u)) then; cu = as_c(u); pu = c_loc(cu); endif
+    if (present(v)) then; cv = as_c(v); pv = c_loc(cv); endif
+    if (present(forcing_z)) pzf = c_loc(forcing_z)
+    if (present(domain_z)) pzd = c_loc(domain_z)
+    if (present(time_varying_z)) tvz = merge(1_c_int, 0_c_int, time_varying_z)
+    call check(icar_hip_forcing_configure(ctx%p, c_loc(cm), pu, pv, int(nsmooth,c_int), pzf, pzd, tvz), "forcing_configure")
+  contains
+    function as_c(g) result(c)
+      type(hip_forcing_geo_t), intent(in), target :: g
+      type(forcing_geo_c) :: c
+      c%x = c_loc(g%x); c%y = c_loc(g%y); c%w = c_loc(g%w); c%z = c_loc(g%z); c%zw = c_loc(g%zw)
+      c%nx = int(size(g%x,2),c_int); c%ny = int(size(g%x,3),c_int)
+      c%nx_f = int(g%nx_f,c_int); c%nz_f = int(g%nz_f,c_int); c%ny_f = int(g%ny_f,c_int); c%i0 = int(g%i0,c_int); c%j0 = int(g%j0,c_int)
+    end function
+  end subroutine
+
+  !> input_data%data_3d of the forcing variable of `field`, as boundary%update_forcing has just read it
+  subroutine hip_forcing_upload(ctx, field, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: field
+    real(c_float), intent(in), target, contiguous :: a(:,:,:)
+    call check(icar_hip_forcing_upload(ctx%p, field, c_loc(a), int(size(a,1),c_int), int(size(a,2),c_int), int(size(a,3),c_int)), "forcing_upload")
+  end subroutine
+
+  !> domain%interpolate_forcing(forcing, update) (domain_obj.f90:2559-2643) over the listed 3-D fields; pressure_field < 0: none
+  subroutine hip_interpolate_forcing(ctx, fields, pressure_field, theta_field, update)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: fields(:), pressure_field, theta_field
+    logical, intent(in) :: update
+    call check(icar_hip_interpolate_forcing(ctx%p, fields, int(size(fields),c_int), pressure_field, theta_field, merge(1_c_int, 0_c_int, update)), &
+               "interpolate_forcing")
+  end subroutine
+
+  !> domain%update_delta_fields(dt) (domain_obj.f90:2339-2372); w is always included
+  subroutine hip_update_delta_fields(ctx, fields, dt_seconds)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: fields(:)
+    double precision, intent(in) :: dt_seconds
+    call check(icar_hip_update_delta_fields(ctx%p, fields, int(size(fields),c_int), real(dt_seconds,c_double)), "update_delta_fields")
+  end subroutine
+
+  !> driver.f90:133-137 behind boundary%update_forcing: interpolate_forcing(update=.True.), update_winds, update_delta_fields
+  subroutine hip_forcing_step(ctx, fields, pressure_field, theta_field, windtype, wind_iterations, dx, halo, dt_seconds)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: fields(:), pressure_field, theta_field
+    integer, intent(in) :: windtype, wind_iterations, halo
+    real, intent(in) :: dx
+    double precision, intent(in) :: dt_seconds
+    call check(icar_hip_forcing_step(ctx%p, fields, int(size(fields),c_int), pressure_field, theta_field, int(windtype,c_int), &
+               int(wind_iterations,c_int), real(dx,c_float), int(halo,c_int), real(dt_seconds,c_double)), "forcing_step")
   end subroutine
 
   !> variable%meta_data%dqdt_3d -> device (the forcing tendency apply_forcing adds)

@@ -649,6 +649,53 @@ int icar_hip_linwinds_perturbation_upload(icar_hip_ctx *ctx, int component, cons
  * CLOUD_ICE, RAIN, SNOW are on the device ("associated"); writes NSQUARED. */
 int icar_hip_spatial_winds(icar_hip_ctx *ctx, int update);
 
+/* ---- F2: the forcing update of the outer loop (src/main/driver.f90:133-137) ---------------------------------------------------------
+ * After boundary%update_forcing (the NetCDF read, which stays with the host) the host uploads the small low-resolution arrays it has
+ * just read and the device turns them into dqdt_3d rates; nothing of the model state crosses the bus.
+ * icar_hip_forcing_configure: the look-up tables the reference builds at init time (geo_LUT, src/utilities/geo_reader.f90:903-976; vLUT,
+ *     src/utilities/vinterp.f90:101-152) for forcing%geo (mass grid: nx, ny the context's tile), forcing%geo_u and %geo_v (the EXTENDED
+ *     staggered grids u_grid2d_ext / v_grid2d_ext, src/objects/domain_obj.f90:2177-2182; i0, j0 = u_grid%ims - u_grid2d_ext%ims and
+ *     u_grid%jms - u_grid2d_ext%jms, likewise for v; both NULL: u and v cannot be forced), domain%nsmooth, and forcing%geo%z (nx, nz_f, ny)
+ *     with domain%geo%z (nx, nz, ny) for adjust_pressure (both NULL: the pressure cannot be forced).  Arrays in Fortran element order, as
+ *     the reference holds them: x, y, w (4, nx, ny); z, zw (2, nx, nz, ny), nz the context's.  EVERY index is checked on the host before
+ *     anything is stored -- x in 1..nx_f, y in 1..ny_f, z in 1..nz_f, the mass tables' extents against the context, the tile inside the
+ *     extended grid, nsmooth within 1..the extended grid's width (smooth_array reads rowmeans(2:windowsize)), and nz_f >= nz when
+ *     forcing%geo%z is given (adjust_pressure indexes it with the model's nz; the reference reads out of bounds otherwise) -- and a bad
+ *     table is refused with a message that names the array and the element.  time_varying_z != 0 is refused: not built.
+ * icar_hip_forcing_upload: input_data%data_3d of the forcing variable of `field`, (nx_f, nz_f, ny_f), as just read.  _download reads
+ *     it back (tests: interpolate_variable smooths the forcing's own u / v IN PLACE, :2775, :2798, and so does the device copy).
+ * icar_hip_interpolate_forcing == domain%interpolate_forcing(forcing, update) (domain_obj.f90:2559-2643) over the listed 3-D fields
+ *     (variables_to_force): update != 0 writes their dqdt_3d mirrors (created if needed), update == 0 the fields themselves
+ *     (get_initial_conditions).  Mass-grid fields: geo_interp (geo_reader.f90:1069-1136) and vinterp (vinterp.f90:284-295), fused, all of
+ *     them in one launch.  ICAR_F_U / ICAR_F_V: smooth_array(input, 1) on the forcing's array in place, geo_interp onto the extended
+ *     grid, vinterp, smooth_array(.., nsmooth), the tile's sub-box (:2764-2806).  pressure_field (-1: none): no vertical interpolation
+ *     (:2750-2760), then adjust_pressure (:2656-2702, update_pressure src/utilities/atm_utilities.f90:611-653) with the forcing data of
+ *     theta_field likewise not interpolated vertically.  Bit-identical to the compiled reference.  Refused before any launch: a call
+ *     before forcing_configure, a 2-D field (geo_interp2d is not built), a field without forcing data or with data of other extents
+ *     than its tables, u / v or the pressure without their tables.
+ * icar_hip_update_delta_fields == domain%update_delta_fields(dt) (:2339-2372): dqdt_3d = (dqdt_3d - data_3d) / dt%seconds() for the
+ *     listed fields and for ICAR_F_W, always (:2368-2369); the difference in REAL(4), the quotient in REAL(8) as dt%seconds() is
+ *     (src/utilities/time_delta_obj.f90:123-130), rounded once.
+ * icar_hip_forcing_step == driver.f90:133-137 in one call: interpolate_forcing(update = 1), icar_hip_update_winds(.., update = 1),
+ *     update_delta_fields; the same bits as the three calls made one after the other. */
+typedef struct icar_hip_forcing_geo {
+    const int *x, *y;              /* geolut%x, %y  INTEGER (4, nx, ny): 1-based indices into the forcing grid       */
+    const float *w;                /* geolut%w      REAL    (4, nx, ny); w(4) is never read                          */
+    const int *z;                  /* vert_lut%z    INTEGER (2, nx, nz, ny): 1-based forcing levels                   */
+    const float *zw;               /* vert_lut%w    REAL    (2, nx, nz, ny)                                          */
+    int nx, ny;                    /* the tables' grid: the tile (mass) or the extended staggered grid (u, v)        */
+    int nx_f, nz_f, ny_f;          /* extents of the forcing arrays these tables index                               */
+    int i0, j0;                    /* u, v: 0-based offset of the tile's staggered grid in the extended grid         */
+} icar_hip_forcing_geo;
+int icar_hip_forcing_configure(icar_hip_ctx *ctx, const icar_hip_forcing_geo *mass, const icar_hip_forcing_geo *u, const icar_hip_forcing_geo *v,
+                               int nsmooth, const float *forcing_z, const float *domain_z, int time_varying_z);
+int icar_hip_forcing_upload(icar_hip_ctx *ctx, int field, const float *lo, int nx_f, int nz_f, int ny_f);
+int icar_hip_forcing_download(icar_hip_ctx *ctx, int field, float *lo, size_t count);
+int icar_hip_interpolate_forcing(icar_hip_ctx *ctx, const int *fields, int nfields, int pressure_field, int theta_field, int update);
+int icar_hip_update_delta_fields(icar_hip_ctx *ctx, const int *fields, int nfields, double dt_seconds);
+int icar_hip_forcing_step(icar_hip_ctx *ctx, const int *fields, int nfields, int pressure_field, int theta_field, int windtype,
+                          int wind_iterations, float dx, int halo, double dt_seconds);
+
 /* ---- H1: halo faces (src/objects/exchangeable_obj.f90:138-356) --------------------------------
  * dir: 0=north 1=south 2=east 3=west.  pack gathers what exchangeable%put_<dir> would PUT
  * (my interior planes next to that edge, width halo, N/S over the full memory width so corners
