@@ -47,15 +47,11 @@
 // pass's U and W come with the denominators).  The same values, loaded by 34 instructions per step instead of 81: 16 face
 // tuples, 5 cell tuples, W of the slot below the wave, V of the next plane's north face and the 7 slots of the scalar.
 #include "ctx.h"
+#include "mpdata_geometry.h"          // MP_HL, MP_XOUT, MP_NW, MP_KB, MP_ZH and the host's layout of a launch
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
 
-#define MP_HL 3                       // halo lanes per side
-#define MP_XOUT (64 - 2 * MP_HL)      // outputs per 64-lane tile
-#define MP_NW 8                       // waves per block at most: two per SIMD, ~250 VGPRs each (12 x 3 levels at three per SIMD: no faster, profiles/r05_steps.md)
-#define MP_KB 5                       // levels per thread at most
-#define MP_ZH 2                       // halo levels of a level range: a fake edge corrupts the outputs of the 2 levels next to it
 #define EPSQ 1e-10f
 #define EPSF 1e-15f
 #define HEPSQ 0.5e-10f                // every cross-term denominator is the sum of TWO stencil sums + EPSQ: each sum carries half of it
@@ -749,31 +745,10 @@ int icar_mpdata_fused_run(icar_hip_ctx *c, bool rho_on, bool fct, bool pass1, co
     if (!c->mpc || c->mpc_dens != (rho_on ? 1 : 0)) { icar_set_error("mpdata: icar_hip_setup_winds(scheme 2) with the same advect_density must come first"); return 1; }
     if (nx < 3 || ny < 3) { icar_set_error("mpdata: tile must be at least 3 x 3 cells"); return 1; }
     if ((size_t)nx * nz * ny * sizeof(float) >= ((size_t)1 << 31)) { icar_set_error("mpdata: a field of 2 GiB or more is not supported (32-bit buffer offsets)"); return 1; }
-    const int ntile = std::max(1, (nx - 2 + MP_XOUT - 1) / MP_XOUT);
-    // levels: one block holds at most MP_NW x MP_KB = 40; taller columns are cut into level ranges with MP_ZH halo levels.  Every
-    // range's block computes its kstore levels and MP_ZH halo levels on either side, so it is those kstore + 2 MP_ZH that must fit
-    // (counting the halos once per cut let nz = 73..76, 109..112, ... through with 6 levels per thread: no such kernel)
-    const int cap_lv = MP_NW * MP_KB;
-    int nkr = 1;
-    while ((nz + nkr - 1) / nkr + (nkr > 1 ? 2 * MP_ZH : 0) > cap_lv) ++nkr;
-    const int kstore = (nz + nkr - 1) / nkr;
-    const int blk_lv = std::min(nz, kstore + (nkr > 1 ? 2 * MP_ZH : 0));       // levels a block computes
-    const int kb = (blk_lv + MP_NW - 1) / MP_NW, nw = (blk_lv + kb - 1) / kb;
-    // y chunks: a block keeps a whole CU, so the work items (tiles x chunks x ranges x scalars) should fill a whole number of
-    // rounds of the 256 CUs; each chunk pays ~3.5 warm-up planes.  Pick the chunk count with the best product of the two.
-    const int rows = ny - 2, per = ntile * nkr * nv;
-    int nchunk = 1; double best = -1.0;
-    for (int n = 1; n <= std::max(1, rows / 16); ++n) {
-        const int cl = (rows + n - 1) / n, nn = (rows + cl - 1) / cl;
-        const double items = (double)per * nn, rounds = std::ceil(items / 256.0);
-        const double eff = items / (256.0 * rounds) * cl / (cl + 3.5);
-        if (eff > best + 1e-9) { best = eff; nchunk = nn; }
-    }
-    const int clen = (rows + nchunk - 1) / nchunk;
-    nchunk = (rows + clen - 1) / clen;
-    const bool exact = (nkr == 1) && (kb * nw == nz);          // the waves hold exactly the column: no per-slot level tests
-#define KBCASE(K) case K: launch_fused<K>(c, fct, pass1, exact, in, out, nv, nw, clen, ntile, nchunk, nkr, kstore); break;
-    switch (kb) { KBCASE(1) KBCASE(2) KBCASE(3) KBCASE(4) KBCASE(5) default: icar_set_error("mpdata: internal level-range error"); return 1; }
+    // x tiles, level ranges, levels per thread, waves and y chunks: mpdata_geometry.h
+    const MpLayout L = mpdata_layout(nx, nz, ny, nv);
+#define KBCASE(K) case K: launch_fused<K>(c, fct, pass1, L.exact, in, out, nv, L.nw, L.clen, L.ntile, L.nchunk, L.nkr, L.kstore); break;
+    switch (L.kb) { KBCASE(1) KBCASE(2) KBCASE(3) KBCASE(4) KBCASE(5) default: icar_set_error("mpdata: internal level-range error"); return 1; }
 #undef KBCASE
     HIPCHK(hipGetLastError());
     return 0;

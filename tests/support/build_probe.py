@@ -1,5 +1,6 @@
 """Builds tests/support/libicar_probe.so (th_probe.hip: the level code's device math functions evaluated on arrays; mpdata_probe.hip:
-zeroes the antidiffusive coefficients of a context so that the fused MPDATA kernel returns its donor-cell pass; wsm_fall_probe.hip:
+zeroes the antidiffusive coefficients of a context so that the fused MPDATA kernel returns its donor-cell pass, and reports the
+launch layout and march schedule of mpdata_geometry.h; wsm_fall_probe.hip:
 the semi-Lagrangian fall of WSM3 / WSM6 on independent columns, in its serial and in its wave form) with the
 product's own compile flags.  TEST INFRASTRUCTURE: called by __graft_entry__.build() (so that the file travels to the GPU box with
 the other built libraries) and by the tests' `probe` fixture.  Cross-compiles without a GPU."""
@@ -29,6 +30,7 @@ def lib():
     L.icar_probe_math.argtypes = [ci, ci, vp, vp, vp]
     L.icar_probe_dec_index.argtypes = [vp, vp, ci, ci, ci, vp]
     L.icar_probe_mpdata_zero_antidiffusion.argtypes = [vp]
+    L.icar_probe_mpdata_geometry.argtypes = [ci, ci, ci, ci, vp]
     L.icar_probe_launch_geometry.argtypes = [ci, vp, vp, vp, vp, vp]
     L.icar_probe_wsm_fall.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     return L

@@ -18,25 +18,12 @@ from icar_amd.capi import lib, check
 from icar_amd.constants import kADV_UPWIND, kADV_MPDATA
 from util import (SCALARS, MEMBER, KVAR, MPDATA_RTOL, MPDATA_MARGIN, bits_equal, nbitdiff, single_image_domain, adv_args, assert_fields_close,
                   roughen_winds)
+from mpdata_rows_case import column_case          # (the tile of these sweeps; the horizontal sweeps build theirs from it)
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ["water_vapor", "cloud_water", "potential_temperature"]
 HEIGHTS = range(2, 121)
-
-
-def column_case(oracle, nz, nx=70, ny=10):
-    """A 70 x 10 tile (two x tiles of the fused kernel, one of them partial; steady and generic steps of the y march) of nz levels.
-    The level thicknesses differ from level to level (100 .. 300 m: a level read from the wrong slot shows), the top stays below
-    25 km (the ideal case's own profile reaches the top of its pressure formula near 90 levels), and u, v carry white noise
-    (w rebalanced), so that the limiter works on nearly every face."""
-    f32 = np.float32
-    c = ideal.make_case(nx, ny, nz, hill_height=1000.0, noise=0.01, n_hydro=1, uniform_dz=200.0)
-    dzl = (f32(100.0) + f32(50.0) * ((np.arange(nz) * 3) % 5).astype(f32)).astype(f32)
-    c["dz_levels"] = dzl
-    c["advection_dz"] = np.ascontiguousarray(np.broadcast_to(dzl[None, :, None], (ny, nz, nx))).astype(f32)
-    c["dz_mass"] = (c["advection_dz"] * c["jacobian"]).astype(f32)
-    return roughen_winds(c, oracle, 0.5)
 
 
 def device_advect(c, names, dt, dens=False, order=2, fct=True, nsteps=1, exact_mode=False, scheme=kADV_MPDATA):
@@ -87,15 +74,15 @@ def check_close(got, ref, what, record=None):
         assert_fields_close(got[n], ref[n], f"{what} {n}", record=None if record is None else ("mpdata_columns", record))
 
 
-def sweep(run, heights=HEIGHTS):
-    """run(nz) at every height; the heights that fail, and how, in one message"""
+def sweep(run, heights=HEIGHTS, what="column heights", key="nz="):
+    """run(nz) at every height (or run(x) at every x of another list: what, key); those that fail, and how, in one message"""
     bad = {}
     for nz in heights:
         try:
             run(nz)
         except (AssertionError, RuntimeError) as e:
             bad[nz] = str(e).splitlines()[0][:200]
-    assert not bad, f"{len(bad)} of {len(heights)} column heights fail: " + "; ".join(f"nz={k}: {v}" for k, v in bad.items())
+    assert not bad, f"{len(bad)} of {len(heights)} {what} fail: " + "; ".join(f"{key}{k}: {v}" for k, v in bad.items())
 
 
 def test_every_column_height_fused(oracle):

@@ -8,10 +8,11 @@ SCALARS = ["water_vapor", "cloud_water", "rain", "snow", "potential_temperature"
            "ice_number", "rain_number"]
 MEMBER = {"water_vapor": "water_vapor", "cloud_water": "cloud_water_mass", "rain": "rain_mass", "snow": "snow_mass",
           "potential_temperature": "potential_temperature", "cloud_ice": "cloud_ice_mass", "graupel": "graupel_mass",
-          "ice_number": "cloud_ice_number", "rain_number": "rain_number"}
+          "ice_number": "cloud_ice_number", "rain_number": "rain_number", "snow_number": "snow_number", "graupel_number": "graupel_number"}
 KVAR = {"water_vapor": "water_vapor", "cloud_water": "cloud_water", "rain": "rain_in_air", "snow": "snow_in_air",
         "potential_temperature": "potential_temperature", "cloud_ice": "cloud_ice", "graupel": "graupel_in_air",
-        "ice_number": "ice_number_concentration", "rain_number": "rain_number_concentration"}
+        "ice_number": "ice_number_concentration", "rain_number": "rain_number_concentration",
+        "snow_number": "snow_number_concentration", "graupel_number": "graupel_number_concentration"}
 
 
 # what the session's comparisons were (tests/conftest.py prints the totals at the end of a `-m gpu` run): fields compared bit for
