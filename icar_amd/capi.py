@@ -34,6 +34,7 @@ SYMBOLS = [
     "icar_hip_pbl_init", "icar_hip_ysu_sfc", "icar_hip_ysu", "icar_hip_ysu_upload", "icar_hip_ysu_download",
     "icar_hip_ra_simple", "icar_hip_rad_configure", "icar_hip_rad_calendar", "icar_hip_rad",
     "icar_hip_lsm_configure", "icar_hip_diag_10m", "icar_hip_water_simple", "icar_hip_apply_fluxes", "icar_hip_lsm", "icar_hip_lsm_layers",
+    "icar_hip_noah_tables", "icar_hip_lsm_init", "icar_hip_lsm_noah", "icar_hip_noah_upload", "icar_hip_noah_download",
     "icar_hip_cu_configure", "icar_hip_cu_bmj", "icar_hip_convect", "icar_hip_cu_reset", "icar_hip_cu_upload", "icar_hip_cu_download", "icar_hip_cu_tables",
     "icar_hip_cu_init", "icar_hip_cu_tiedtke", "icar_hip_tiedtke_upload", "icar_hip_tiedtke_download",
     "icar_hip_convection_init", "icar_hip_cu_nsas", "icar_hip_nsas_upload", "icar_hip_nsas_download",
@@ -57,6 +58,26 @@ class forcing_geo_c(ctypes.Structure):         # struct icar_hip_forcing_geo (in
     _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("w", ctypes.c_void_p), ("z", ctypes.c_void_p), ("zw", ctypes.c_void_p),
                 ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("nx_f", ctypes.c_int), ("nz_f", ctypes.c_int), ("ny_f", ctypes.c_int),
                 ("i0", ctypes.c_int), ("j0", ctypes.c_int)]
+
+
+# struct icar_hip_noah_tables_t (include/icar_hip.h): module_sf_noahlsm's table variables, NLUS = 50, NSLTYPE = 30, NSLOPE = 30 elements
+NOAH_NLUS, NOAH_NSLTYPE, NOAH_NSLOPE = 50, 30, 30
+NOAH_T_VEG = ["snuptbl", "rstbl", "rgltbl", "hstbl", "maxalb", "emissmintbl", "emissmaxtbl", "laimintbl", "laimaxtbl", "z0mintbl", "z0maxtbl",
+              "albedomintbl", "albedomaxtbl"]
+NOAH_T_SOIL = ["bb", "drysmc", "f11", "maxsmc", "refsmc", "satpsi", "satdk", "satdw", "wltsmc", "qtz"]
+NOAH_T_GEN = ["topt_data", "cmcmax_data", "cfactr_data", "rsmax_data", "sbeta_data", "fxexp_data", "csoil_data", "salp_data", "refdk_data",
+              "refkdt_data", "frzk_data", "zbot_data", "lvcoef_data"]
+NOAH_T_INT = ["bare", "lucats", "slcats", "slpcats"]
+
+
+class noah_tables_c(ctypes.Structure):
+    _fields_ = ([("nrotbl", ctypes.c_void_p)] + [(n, ctypes.c_void_p) for n in NOAH_T_VEG + NOAH_T_SOIL + ["slope_data"]]
+                + [(n, ctypes.c_float) for n in NOAH_T_GEN] + [(n, ctypes.c_int) for n in NOAH_T_INT])
+
+
+class noah_options_c(ctypes.Structure):        # struct icar_hip_noah_options_t (include/icar_hip.h)
+    _fields_ = [("urban_category", ctypes.c_int), ("ice_category", ctypes.c_int), ("water_category", ctypes.c_int), ("lake_category", ctypes.c_int),
+                ("monthly_vegfrac", ctypes.c_int), ("monthly_albedo", ctypes.c_int), ("fndsnowh", ctypes.c_int), ("max_swe", ctypes.c_float)]
 
 
 N_ADVECTABLE = 11
@@ -132,6 +153,11 @@ def lib():
         L.icar_hip_lsm.argtypes = [vp, ctypes.c_float]
         L.icar_hip_lsm_layers.argtypes = [vp, ctypes.POINTER(ci)]
         cf = ctypes.c_float
+        L.icar_hip_noah_tables.argtypes = [vp, ctypes.POINTER(noah_tables_c)]
+        L.icar_hip_lsm_init.argtypes = [vp, ci, ci, ci, cf, cf, cf, ctypes.POINTER(noah_options_c)]
+        L.icar_hip_lsm_noah.argtypes = [vp, cf, ci, ci, ci, ci]
+        L.icar_hip_noah_upload.argtypes = [vp, ci, vp]
+        L.icar_hip_noah_download.argtypes = [vp, ci, vp]
         L.icar_hip_cu_configure.argtypes = [vp, ci, cf, cf, cf, cf, cf, cf]
         L.icar_hip_cu_bmj.argtypes = [vp, cf, ci, ci, ci, ci]
         L.icar_hip_convect.argtypes = [vp, cf]

@@ -29,6 +29,7 @@ struct IcarComm;         // comm.hip
 struct CuState;          // cu_bmj.hip
 struct YsuState;         // pbl_ysu.hip
 struct ForcingState;     // forcing.hip
+struct NoahState;        // lsm_noah.hip
 
 // state of the step driver (timestep.hip): the options / grid members the sub-step loop reads, the model clock, and what
 // mp_driver.f90 keeps in SAVE variables (last_model_time)
@@ -111,6 +112,7 @@ struct icar_hip_ctx {
     float sfc_nz_thick = 0.0f;
     unsigned *sfc_levelmax = nullptr;
     CuState *cu = nullptr;               // cu_bmj.hip: the convection slot's arrays, BMJINIT's tables and the column workspace
+    NoahState *noah = nullptr;           // lsm_noah.hip: the Noah tables and the model's own arrays (ICAR_NOAH_*)
     YsuState *ysu = nullptr;             // pbl_ysu.hip: pbl_init's arrays, the scheme's results and tendencies, the column workspace
     // reductions / flags
     float *d_red = nullptr;              // small device scratch for reductions
@@ -187,6 +189,8 @@ int icar_sfc_layers(icar_hip_ctx *c, int kts, int kte, int *nz_out);
 int icar_sfc_apply_fluxes_run(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte);
 int icar_lsm_run(icar_hip_ctx *c, float dt);                                // lsm(domain, options, dt): the gate, water_simple, apply_fluxes on the step's tile
 int icar_lsm_init_device(icar_hip_ctx *c);
+// lsm_noah.hip
+void icar_noah_free(icar_hip_ctx *c);
 // cu_bmj.hip
 void icar_cu_free(icar_hip_ctx *c);
 int icar_cu_init_device(icar_hip_ctx *c);                                   // init_convection for kCU_BMJ: arrays, tables, workspace

@@ -119,6 +119,35 @@ GF_FN float gf_expf(float x)
     return res;
 }
 
+// ---- exp2f (e_exp2f.c, FMA build): what LLVM makes of 2.0 ** x (noah_column.h: TDFCND's THKO ** (1. - QZ)) -------------------
+GF_FN float gf_exp2f_special(float x, float main_value)
+{   // |x| >= 128 or NaN
+    if (gf_asuint(x) == 0xff800000u) return 0.0f;              // exp2(-inf)
+    if (((gf_asuint(x) >> 20) & 0x7ff) >= 0x7f8) return x + x;  // +inf, NaN
+    if (x > 0.0f) return __builtin_inff();                     // overflow
+    if (x <= -150.0f) return 0.0f;                             // underflow
+    if (x < -149.0f) return 0x1p-149f;                         // __math_may_uflowf
+    return main_value;                                         // -149 <= x <= -128: a subnormal result, from the formula
+}
+GF_FN float gf_exp2f(float x)
+{
+    const double Shift = 0x1.8p+52 / 32,
+                 C0 = 0x1.c6af84b912394p-5, C1 = 0x1.ebfce50fac4f3p-3, C2 = 0x1.62e42ff0c52d6p-1;     // __exp2f_data.poly
+    const double xd = (double)x;
+    double kd = xd + Shift;                                    // x = k/32 + r with r in [-1/64, 1/64]
+    const uint32_t ki = (uint32_t)gf_asuint64(kd);
+    kd -= Shift;
+    const double r = xd - kd;
+    const double s = gf_scale(ki, 0);
+    const double z = __builtin_fma(C0, r, C1);
+    const double r2 = r * r;
+    double y = __builtin_fma(C2, r, 1.0);
+    y = __builtin_fma(z, r2, y);
+    float res = (float)(y * s);
+    if (GF_UNLIKELY(((gf_asuint(x) >> 20) & 0x7ff) >= 0x430)) res = gf_exp2f_special(x, res);
+    return res;
+}
+
 // ---- logf (e_logf.c, FMA build) ----------------------------------------------------------------------------------------
 GF_FN float gf_logf_main(uint32_t ix)
 {   // a positive normal x as its bit pattern (exponent possibly below the normal range after the subnormal shift); log(1) = +0

@@ -337,6 +337,11 @@ int icar_lsm_run(icar_hip_ctx *c, float dt)
 {
     IcarStepState &s = c->step;
     if (s.landsurface == 0) return 0;                                 // :1014, whatever watersurface is
+    if (s.landsurface == ICAR_LSM_NOAH) {
+        icar_set_error("lsm: the Noah branch of lsm() (lsm_driver.f90:1177-1291: CHS, QGH, current_precipitation, the statements after the call, "
+                       "soil_totalmoisture, surface_diagnostics) is not built: Noah runs through icar_hip_lsm_noah only");
+        return 1;
+    }
     const double now = s.model_time, upd = (double)s.lsm_update_interval;
     if (s.lsm_last_model_time == -999.0) s.lsm_last_model_time = now - upd;                          // :1016-1018
     if ((now - s.lsm_last_model_time) >= upd) {                                                      // :1021

@@ -48,6 +48,16 @@ static bool cfg_ok(icar_hip_ctx *c, const char *who)
     return false;
 }
 
+// looked at before a step issues anything: the lsm slot of a sub-step cannot run Noah (sfc_basic.hip: icar_lsm_run), and a step that
+// found that out in its lsm slot would have run diagnostic_update and rad already
+static bool lsm_slot_ok(icar_hip_ctx *c, const char *who)
+{
+    if (c->step.landsurface != ICAR_LSM_NOAH) return true;
+    icar_set_error(std::string(who) + ": landsurface = 3 (kLSM_NOAH): the Noah branch of lsm() (lsm_driver.f90:1177-1291) is not built, so the step's lsm slot "
+                   "cannot run: Noah runs through icar_hip_lsm_noah only");
+    return false;
+}
+
 // ---- M0: mp(domain, options, dt, halo, subset) (mp_driver.f90:673-772) ------------------------------------------------
 // exner_from_p: Thompson computes exner from the pressure (a sub-step whose diagnostic kernel was left out, lazy_diag_part below)
 static int process_subdomain(icar_hip_ctx *c, float dt, int its, int ite, int jts, int jte, int kts, int kte, bool exner_from_p)
@@ -615,7 +625,7 @@ int icar_hip_lsm_configure(icar_hip_ctx *c, int landsurface, int watersurface, i
 {
     // the values are looked at first: a host learns what is not built without a device
     if (landsurface == 2) { icar_set_error("lsm_configure: landsurface = 2 (kLSM_SIMPLE): the reference stops here with \"Simple LSM not settup, choose a different LSM options\" (lsm_driver.f90:615); 0 or 1 (kLSM_BASIC)"); return 1; }
-    if (landsurface == 3) { icar_set_error("lsm_configure: landsurface = 3 (kLSM_NOAH) is not built; 0 or 1 (kLSM_BASIC)"); return 1; }
+    if (landsurface == 3) { icar_set_error("lsm_configure: landsurface = 3 (kLSM_NOAH) is not built behind this entry point (it needs the tables and options%lsm_options): icar_hip_lsm_init takes it; 0 or 1 (kLSM_BASIC)"); return 1; }
     if (landsurface == 4) { icar_set_error("lsm_configure: landsurface = 4 (kLSM_NOAHMP) is not built; 0 or 1 (kLSM_BASIC)"); return 1; }
     if (landsurface < 0 || landsurface > 4) { icar_set_error("lsm_configure: landsurface is 0 or 1 (kLSM_BASIC)"); return 1; }
     if (watersurface == 3) { icar_set_error("lsm_configure: watersurface = 3 (kWATER_LAKE) is not built; 0, 1 (kWATER_BASIC, nothing runs) or 2 (kWATER_SIMPLE)"); return 1; }
@@ -880,7 +890,7 @@ int icar_hip_update_dt(icar_hip_ctx *c, double *dt_seconds)
 int icar_hip_substep(icar_hip_ctx *c, double dt_seconds, int enforce_limits)
 {
     if (!c) { icar_set_error("substep: null argument"); return 1; }
-    if (!cfg_ok(c, "substep")) return 1;
+    if (!cfg_ok(c, "substep") || !lsm_slot_ok(c, "substep")) return 1;
     if (c->on_aux) { icar_set_error("substep: called between aux_begin and aux_end"); return 1; }
     HIPCHK(hipSetDevice(c->device));
     return icar_substep(c, dt_seconds, enforce_limits != 0, true);
@@ -891,7 +901,7 @@ int icar_hip_substep(icar_hip_ctx *c, double dt_seconds, int enforce_limits)
 int icar_hip_step_n(icar_hip_ctx *c, int nsteps, double *dt_last)
 {
     if (!c) { icar_set_error("step_n: null argument"); return 1; }
-    if (!cfg_ok(c, "step_n")) return 1;
+    if (!cfg_ok(c, "step_n") || !lsm_slot_ok(c, "step_n")) return 1;
     if (c->on_aux) { icar_set_error("step_n: called between aux_begin and aux_end"); return 1; }
     HIPCHK(hipSetDevice(c->device));
     double dt = 0.0;
@@ -909,7 +919,7 @@ int icar_hip_step_n(icar_hip_ctx *c, int nsteps, double *dt_last)
 int icar_hip_step(icar_hip_ctx *c, double end_time_seconds, int *nsteps)
 {
     if (!c) { icar_set_error("step: null argument"); return 1; }
-    if (!cfg_ok(c, "step")) return 1;
+    if (!cfg_ok(c, "step") || !lsm_slot_ok(c, "step")) return 1;
     if (c->on_aux) { icar_set_error("step: called between aux_begin and aux_end"); return 1; }
     HIPCHK(hipSetDevice(c->device));
     int n = 0;

@@ -27,6 +27,15 @@ module icar_hip
             ICAR_YSU_TEND_QI, ICAR_YSU_TEND_U, ICAR_YSU_TEND_V, ICAR_YSU_N, &
             hip_pbl_configure, hip_pbl, hip_pbl_simple, ICAR_PBL_SIMPLE, hip_rad_configure, hip_rad_calendar, hip_rad, hip_ra_simple, ICAR_RA_SIMPLE, &
             hip_lsm_configure, hip_diag_10m, hip_water_simple, hip_apply_fluxes, hip_lsm, hip_lsm_layers, ICAR_LSM_BASIC, ICAR_WATER_SIMPLE, &
+            hip_noah_tables_t, hip_noah_options_t, hip_noah_tables, hip_lsm_init, hip_lsm_noah, hip_noah_upload, hip_noah_upload_int, hip_noah_download, &
+            hip_noah_download_int, ICAR_LSM_NOAH, &
+            ICAR_NOAH_VEG_TYPE, ICAR_NOAH_SOIL_TYPE, ICAR_NOAH_VEGFRAC, ICAR_NOAH_SOIL_DEEP_TEMPERATURE, ICAR_NOAH_SHDMIN, ICAR_NOAH_SHDMAX, &
+            ICAR_NOAH_SNOALB, ICAR_NOAH_QGH, ICAR_NOAH_CHS, ICAR_NOAH_CQS2, ICAR_NOAH_RI, ICAR_NOAH_CURRENT_PRECIPITATION, &
+            ICAR_NOAH_GROUND_HEAT_FLUX, ICAR_NOAH_SMSTAV, ICAR_NOAH_SOIL_TOTALMOISTURE, ICAR_NOAH_SFCRUNOFF, ICAR_NOAH_UDRUNOFF, ICAR_NOAH_ALBEDO, &
+            ICAR_NOAH_ALBBCK, ICAR_NOAH_Z0, ICAR_NOAH_EMISS, ICAR_NOAH_SNOWC, ICAR_NOAH_SNOW_WATER_EQUIVALENT, ICAR_NOAH_SNOW_HEIGHT, &
+            ICAR_NOAH_CANOPY_WATER, ICAR_NOAH_CHS2, ICAR_NOAH_CHKLOWQ, ICAR_NOAH_LAI, ICAR_NOAH_SNOTIME, ICAR_NOAH_ACSNOM, ICAR_NOAH_ACSNOW, &
+            ICAR_NOAH_SNOPCX, ICAR_NOAH_POTEVP, ICAR_NOAH_NOAHRES, ICAR_NOAH_FLX4, ICAR_NOAH_FVB, ICAR_NOAH_FBUR, ICAR_NOAH_FGSN, &
+            ICAR_NOAH_SOIL_WATER_CONTENT, ICAR_NOAH_SOIL_TEMPERATURE, ICAR_NOAH_SH2O, ICAR_NOAH_SMCREL, ICAR_NOAH_N, &
             hip_cu_configure, hip_cu_bmj, hip_convect, hip_cu_reset, hip_cu_upload, hip_cu_download, ICAR_CU_BMJ, ICAR_CU_NO_STOCHASTIC, &
             hip_cu_init, hip_cu_tiedtke, hip_tiedtke_upload, hip_tiedtke_download, hip_tiedtke_download_ktype, ICAR_CU_TIEDTKE, &
             ICAR_TIEDTKE_TEND_QC, ICAR_TIEDTKE_TEND_QI, ICAR_TIEDTKE_PRATEC, ICAR_TIEDTKE_KTYPE, ICAR_TIEDTKE_N, &
@@ -84,6 +93,18 @@ module icar_hip
        ICAR_YSU_PSIH=5, ICAR_YSU_REGIME=6, ICAR_YSU_RI=7, ICAR_YSU_WINDSPD=8, ICAR_YSU_HOL=9, ICAR_YSU_ZOL=10, ICAR_YSU_GZ1OZ0=11, &
        ICAR_YSU_Z_ATM=12, ICAR_YSU_TEND_TH=13, ICAR_YSU_TEND_QV=14, ICAR_YSU_TEND_QC=15, ICAR_YSU_TEND_QI=16, ICAR_YSU_TEND_U=17, &
        ICAR_YSU_TEND_V=18, ICAR_YSU_N=19
+  integer(c_int), parameter :: ICAR_LSM_NOAH = 3        ! kLSM_NOAH, icar_constants.f90
+  ! enum icar_hip_noah_array (include/icar_hip.h): the Noah model's arrays, REAL(4) (nx,ny) but VEG_TYPE / SOIL_TYPE, which are INTEGER(4),
+  ! and the four soil arrays (nx,4,ny)
+  integer(c_int), parameter :: &
+       ICAR_NOAH_VEG_TYPE=0, ICAR_NOAH_SOIL_TYPE=1, ICAR_NOAH_VEGFRAC=2, ICAR_NOAH_SOIL_DEEP_TEMPERATURE=3, ICAR_NOAH_SHDMIN=4, ICAR_NOAH_SHDMAX=5, &
+       ICAR_NOAH_SNOALB=6, ICAR_NOAH_QGH=7, ICAR_NOAH_CHS=8, ICAR_NOAH_CQS2=9, ICAR_NOAH_RI=10, ICAR_NOAH_CURRENT_PRECIPITATION=11, &
+       ICAR_NOAH_GROUND_HEAT_FLUX=12, ICAR_NOAH_SMSTAV=13, ICAR_NOAH_SOIL_TOTALMOISTURE=14, ICAR_NOAH_SFCRUNOFF=15, ICAR_NOAH_UDRUNOFF=16, &
+       ICAR_NOAH_ALBEDO=17, ICAR_NOAH_ALBBCK=18, ICAR_NOAH_Z0=19, ICAR_NOAH_EMISS=20, ICAR_NOAH_SNOWC=21, ICAR_NOAH_SNOW_WATER_EQUIVALENT=22, &
+       ICAR_NOAH_SNOW_HEIGHT=23, ICAR_NOAH_CANOPY_WATER=24, ICAR_NOAH_CHS2=25, ICAR_NOAH_CHKLOWQ=26, ICAR_NOAH_LAI=27, ICAR_NOAH_SNOTIME=28, &
+       ICAR_NOAH_ACSNOM=29, ICAR_NOAH_ACSNOW=30, ICAR_NOAH_SNOPCX=31, ICAR_NOAH_POTEVP=32, ICAR_NOAH_NOAHRES=33, ICAR_NOAH_FLX4=34, ICAR_NOAH_FVB=35, &
+       ICAR_NOAH_FBUR=36, ICAR_NOAH_FGSN=37, ICAR_NOAH_SOIL_WATER_CONTENT=38, ICAR_NOAH_SOIL_TEMPERATURE=39, ICAR_NOAH_SH2O=40, ICAR_NOAH_SMCREL=41, &
+       ICAR_NOAH_N=42
   real(c_float), parameter :: ICAR_CU_NO_STOCHASTIC = -9999.0   ! kNO_STOCHASTIC, icar_constants.f90:340
   ! enum icar_hip_cu_array (include/icar_hip.h): the convection slot's own arrays, REAL(4) (nx,ny) but for the two tendencies (nx,nz,ny)
   integer(c_int), parameter :: ICAR_CU_CLDEFI=0, ICAR_CU_ACC_CONV_PCP=1, ICAR_CU_RAINCV=2, ICAR_CU_CUTOP=3, ICAR_CU_CUBOT=4, &
@@ -95,6 +116,33 @@ module icar_hip
   ! enum icar_hip_nsas_array: the NSAS scheme's own REAL(4) arrays: tend%qc, tend%qi (nx,nz,ny), PRATEC, HBOT, HTOP, hpbl (nx,ny)
   integer(c_int), parameter :: ICAR_NSAS_TEND_QC=0, ICAR_NSAS_TEND_QI=1, ICAR_NSAS_PRATEC=2, ICAR_NSAS_HBOT=3, ICAR_NSAS_HTOP=4, ICAR_NSAS_HPBL=5, &
                                ICAR_NSAS_N=6
+
+  ! struct icar_hip_noah_tables_t (include/icar_hip.h) and what a host fills in: pointers to module_sf_noahlsm's own table variables after
+  ! SOIL_VEG_GEN_PARM has read them (nrotbl => NROTBL, snuptbl => SNUPTBL, ..., bb => BB, ..., slope_data => SLOPE_DATA) and its scalars
+  type, bind(C) :: noah_tables_c
+     type(c_ptr) :: nrotbl, snuptbl, rstbl, rgltbl, hstbl, maxalb, emissmintbl, emissmaxtbl, laimintbl, laimaxtbl, z0mintbl, z0maxtbl, &
+                    albedomintbl, albedomaxtbl, bb, drysmc, f11, maxsmc, refsmc, satpsi, satdk, satdw, wltsmc, qtz, slope_data
+     real(c_float) :: topt_data, cmcmax_data, cfactr_data, rsmax_data, sbeta_data, fxexp_data, csoil_data, salp_data, refdk_data, refkdt_data, &
+                      frzk_data, zbot_data, lvcoef_data
+     integer(c_int) :: bare, lucats, slcats, slpcats
+  end type
+  type hip_noah_tables_t
+     integer(c_int), pointer, contiguous :: nrotbl(:) => null()
+     real(c_float), pointer, contiguous :: snuptbl(:) => null(), rstbl(:) => null(), rgltbl(:) => null(), hstbl(:) => null(), maxalb(:) => null(), &
+          emissmintbl(:) => null(), emissmaxtbl(:) => null(), laimintbl(:) => null(), laimaxtbl(:) => null(), z0mintbl(:) => null(), &
+          z0maxtbl(:) => null(), albedomintbl(:) => null(), albedomaxtbl(:) => null(), bb(:) => null(), drysmc(:) => null(), f11(:) => null(), &
+          maxsmc(:) => null(), refsmc(:) => null(), satpsi(:) => null(), satdk(:) => null(), satdw(:) => null(), wltsmc(:) => null(), &
+          qtz(:) => null(), slope_data(:) => null()
+     real(c_float) :: topt_data, cmcmax_data, cfactr_data, rsmax_data, sbeta_data, fxexp_data, csoil_data, salp_data, refdk_data, refkdt_data, &
+                      frzk_data, zbot_data, lvcoef_data
+     integer(c_int) :: bare, lucats, slcats, slpcats
+  end type
+  !> struct icar_hip_noah_options_t == options%lsm_options as lsm_init reads them for Noah (lsm_driver.f90:633-651, :1280)
+  type, bind(C) :: hip_noah_options_t
+     integer(c_int) :: urban_category = 13, ice_category = 15, water_category = 17, lake_category = 21
+     integer(c_int) :: monthly_vegfrac = 0, monthly_albedo = 0, fndsnowh = 0
+     real(c_float)  :: max_swe = 1.0e10
+  end type
 
   !> struct icar_hip_step_config == the members of options_t / grid_t the sub-step loop reads (time_step.f90:440-551)
   type, bind(C) :: hip_step_config_t
@@ -242,6 +290,23 @@ module icar_hip
      end function
      integer(c_int) function icar_hip_lsm_layers(ctx, nz) bind(C, name="icar_hip_lsm_layers")
        import; type(c_ptr), value :: ctx; integer(c_int) :: nz
+     end function
+     integer(c_int) function icar_hip_noah_tables(ctx, tables) bind(C, name="icar_hip_noah_tables")
+       import; type(c_ptr), value :: ctx; type(noah_tables_c) :: tables
+     end function
+     integer(c_int) function icar_hip_lsm_init(ctx, landsurface, watersurface, update_interval, sh_feedback_fraction, lh_feedback_fraction, &
+                                               sfc_layer_thickness, noah) bind(C, name="icar_hip_lsm_init")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: landsurface, watersurface, update_interval
+       real(c_float), value :: sh_feedback_fraction, lh_feedback_fraction, sfc_layer_thickness; type(hip_noah_options_t) :: noah
+     end function
+     integer(c_int) function icar_hip_lsm_noah(ctx, lsm_dt, its, ite, jts, jte) bind(C, name="icar_hip_lsm_noah")
+       import; type(c_ptr), value :: ctx; real(c_float), value :: lsm_dt; integer(c_int), value :: its, ite, jts, jte
+     end function
+     integer(c_int) function icar_hip_noah_upload(ctx, which, host) bind(C, name="icar_hip_noah_upload")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
+     end function
+     integer(c_int) function icar_hip_noah_download(ctx, which, host) bind(C, name="icar_hip_noah_download")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
      end function
      integer(c_int) function icar_hip_cu_configure(ctx, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, &
                                                    tend_th_fraction, tend_qi_fraction) bind(C, name="icar_hip_cu_configure")
@@ -682,6 +747,74 @@ contains
     call check(icar_hip_lsm_layers(ctx%p, n), "lsm_layers")
     nz = int(n)
   end function
+
+  !> SOIL_VEG_GEN_PARM's results (lsm_noahdrv.f90:1199-1432) to the device: t's pointers are associated with module_sf_noahlsm's arrays
+  subroutine hip_noah_tables(ctx, t)
+    type(hip_ctx_t), intent(in) :: ctx
+    type(hip_noah_tables_t), intent(in) :: t
+    type(noah_tables_c) :: c
+    c%nrotbl = c_loc(t%nrotbl); c%snuptbl = c_loc(t%snuptbl); c%rstbl = c_loc(t%rstbl); c%rgltbl = c_loc(t%rgltbl); c%hstbl = c_loc(t%hstbl)
+    c%maxalb = c_loc(t%maxalb); c%emissmintbl = c_loc(t%emissmintbl); c%emissmaxtbl = c_loc(t%emissmaxtbl); c%laimintbl = c_loc(t%laimintbl)
+    c%laimaxtbl = c_loc(t%laimaxtbl); c%z0mintbl = c_loc(t%z0mintbl); c%z0maxtbl = c_loc(t%z0maxtbl); c%albedomintbl = c_loc(t%albedomintbl)
+    c%albedomaxtbl = c_loc(t%albedomaxtbl); c%bb = c_loc(t%bb); c%drysmc = c_loc(t%drysmc); c%f11 = c_loc(t%f11); c%maxsmc = c_loc(t%maxsmc)
+    c%refsmc = c_loc(t%refsmc); c%satpsi = c_loc(t%satpsi); c%satdk = c_loc(t%satdk); c%satdw = c_loc(t%satdw); c%wltsmc = c_loc(t%wltsmc)
+    c%qtz = c_loc(t%qtz); c%slope_data = c_loc(t%slope_data)
+    c%topt_data = t%topt_data; c%cmcmax_data = t%cmcmax_data; c%cfactr_data = t%cfactr_data; c%rsmax_data = t%rsmax_data; c%sbeta_data = t%sbeta_data
+    c%fxexp_data = t%fxexp_data; c%csoil_data = t%csoil_data; c%salp_data = t%salp_data; c%refdk_data = t%refdk_data; c%refkdt_data = t%refkdt_data
+    c%frzk_data = t%frzk_data; c%zbot_data = t%zbot_data; c%lvcoef_data = t%lvcoef_data
+    c%bare = t%bare; c%lucats = t%lucats; c%slcats = t%slcats; c%slpcats = t%slpcats
+    call check(icar_hip_noah_tables(ctx%p, c), "noah_tables")
+  end subroutine
+
+  !> lsm_init (lsm_driver.f90:522-711) with every landsurface that is built: 0 and ICAR_LSM_BASIC as hip_lsm_configure; ICAR_LSM_NOAH after
+  !! hip_noah_tables and the uploads of the domain's arrays (hip_noah_upload)
+  subroutine hip_lsm_init(ctx, landsurface, watersurface, update_interval, sh_feedback_fraction, lh_feedback_fraction, sfc_layer_thickness, noah)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer, intent(in) :: landsurface, watersurface, update_interval
+    real, intent(in) :: sh_feedback_fraction, lh_feedback_fraction, sfc_layer_thickness
+    type(hip_noah_options_t), intent(in) :: noah
+    type(hip_noah_options_t) :: n
+    n = noah
+    call check(icar_hip_lsm_init(ctx%p, int(landsurface,c_int), int(watersurface,c_int), int(update_interval,c_int), real(sh_feedback_fraction,c_float), &
+                                 real(lh_feedback_fraction,c_float), real(sfc_layer_thickness,c_float), n), "lsm_init")
+  end subroutine
+
+  !> the call of lsm_noah alone (lsm_driver.f90:1210-1278) on a tile
+  subroutine hip_lsm_noah(ctx, lsm_dt, its, ite, jts, jte)
+    type(hip_ctx_t), intent(in) :: ctx
+    real, intent(in) :: lsm_dt
+    integer, intent(in) :: its, ite, jts, jte
+    call check(icar_hip_lsm_noah(ctx%p, real(lsm_dt,c_float), int(its,c_int), int(ite,c_int), int(jts,c_int), int(jte,c_int)), "lsm_noah")
+  end subroutine
+
+  !> the Noah model's arrays by ICAR_NOAH_*: REAL(4) (nx,ny) or (nx,4,ny); ICAR_NOAH_VEG_TYPE / _SOIL_TYPE through the _int pair
+  subroutine hip_noah_upload(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(in), target, contiguous :: a(..)
+    call check(icar_hip_noah_upload(ctx%p, which, c_loc(a)), "noah_upload")
+  end subroutine
+
+  subroutine hip_noah_upload_int(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    integer(c_int), intent(in), target, contiguous :: a(:,:)
+    call check(icar_hip_noah_upload(ctx%p, which, c_loc(a)), "noah_upload")
+  end subroutine
+
+  subroutine hip_noah_download(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(inout), target, contiguous :: a(..)
+    call check(icar_hip_noah_download(ctx%p, which, c_loc(a)), "noah_download")
+  end subroutine
+
+  subroutine hip_noah_download_int(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    integer(c_int), intent(inout), target, contiguous :: a(:,:)
+    call check(icar_hip_noah_download(ctx%p, which, c_loc(a)), "noah_download")
+  end subroutine
 
   !> init_convection (cu_driver.f90:97-253): options%physics%convection (0 or ICAR_CU_BMJ; Tiedtke goes through hip_cu_init, NSAS through hip_convection_init, 2 and 3 have no
   !! branch in the reference) and options%cu_options (stochastic_cu must be kNO_STOCHASTIC; a negative fraction inherits tendency_fraction)

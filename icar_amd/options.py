@@ -46,6 +46,15 @@ class lsm_options_type:                  # opt_types.f90:132-150, defaults optio
     lh_feedback_fraction: float = 1.0
     sh_feedback_fraction: float = 0.625
     sfc_layer_thickness: float = 400.0   # m of atmosphere the fluxes are spread over
+    # what lsm_init reads for kLSM_NOAH (lsm_driver.f90:633-651, :1280); the categories are those of LU_Categories = MODIFIED_IGBP_MODIS_NOAH
+    LU_Categories: str = "MODIFIED_IGBP_MODIS_NOAH"
+    urban_category: int = 13
+    ice_category: int = 15
+    water_category: int = 17
+    lake_category: int = 21
+    monthly_vegfrac: bool = False
+    monthly_albedo: bool = False
+    max_swe: float = 1e10
 
 
 @dataclass

@@ -1,12 +1,25 @@
 """land-surface driver mirror (src/physics/lsm_driver.f90): lsm_var_request / lsm_init / lsm, plus the parts on their own --
 the 10 m diagnostics of diagnostic_update, water_simple and apply_fluxes.
 
-Only landsurface = kLSM_BASIC (fluxes prescribed by the host or the forcing and applied to the atmosphere) with watersurface 0,
-kWATER_BASIC (nothing runs) or kWATER_SIMPLE (src/physics/water_simple.f90: bulk fluxes over open water) is built; kLSM_SIMPLE stops
-in the reference's own lsm_init and is refused with its message, Noah, Noah-MP and the lake model are refused by the library."""
+landsurface = kLSM_BASIC (fluxes prescribed by the host or the forcing and applied to the atmosphere) with watersurface 0,
+kWATER_BASIC (nothing runs) or kWATER_SIMPLE (src/physics/water_simple.f90: bulk fluxes over open water) is built whole; kLSM_SIMPLE stops
+in the reference's own lsm_init and is refused with its message, Noah-MP and the lake model are refused by the library.  Of
+kLSM_NOAH lsm_init's part and the call of lsm_noah are built (noah_tables, noah_init, lsm_noah, noah_set / noah_get); the rest of the
+Noah branch of lsm() is not, and lsm() says so."""
 import ctypes
-from .capi import lib, check
-from .constants import kLSM_BASIC, kWATER_SIMPLE
+
+import numpy as np
+
+from .capi import lib, check, noah_tables_c, noah_options_c, NOAH_T_VEG, NOAH_T_SOIL, NOAH_T_GEN, NOAH_T_INT
+from .constants import kLSM_BASIC, kLSM_NOAH, kWATER_SIMPLE
+
+# enum icar_hip_noah_array (include/icar_hip.h)
+NOAH_ARRAYS = ["veg_type", "soil_type", "vegfrac", "soil_deep_temperature", "shdmin", "shdmax", "snoalb", "qgh", "chs", "cqs2", "ri",
+               "current_precipitation", "ground_heat_flux", "smstav", "soil_totalmoisture", "sfcrunoff", "udrunoff", "albedo", "albbck", "z0", "emiss",
+               "snowc", "snow_water_equivalent", "snow_height", "canopy_water", "chs2", "chklowq", "lai", "snotime", "acsnom", "acsnow", "snopcx",
+               "potevp", "noahres", "flx4", "fvb", "fbur", "fgsn", "soil_water_content", "soil_temperature", "sh2o", "smcrel"]
+NOAH_ID = {n: i for i, n in enumerate(NOAH_ARRAYS)}
+NOAH_SOIL_LAYERS = 4
 
 
 def lsm_var_request(options):
@@ -29,8 +42,58 @@ def lsm_init(domain, options):
     """lsm_init (lsm_driver.f90:522-611, :991-1000): options%physics%landsurface / %watersurface and options%lsm_options to the library;
     QSFC = water_vapor(:,kms,:) when water_vapor is on the device."""
     o = options.lsm_options
+    if options.physics.landsurface == kLSM_NOAH:
+        return noah_init(domain, options)
     lsm_configure(domain, options.physics.landsurface, options.physics.watersurface, o.update_interval, o.sh_feedback_fraction,
                   o.lh_feedback_fraction, o.sfc_layer_thickness)
+
+
+def noah_tables(domain, tab):
+    """icar_hip_noah_tables: the tables as SOIL_VEG_GEN_PARM parsed them -- tab maps module_sf_noahlsm's variable names (lower case) to
+    arrays of the module's extents and scalars"""
+    t, keep = noah_tables_c(), []
+    for n, dt_ in [("nrotbl", np.int32)] + [(n, np.float32) for n in NOAH_T_VEG + NOAH_T_SOIL + ["slope_data"]]:
+        a = np.ascontiguousarray(tab[n], dt_); keep.append(a)
+        setattr(t, n, a.ctypes.data)
+    for n in NOAH_T_GEN: setattr(t, n, float(tab[n]))
+    for n in NOAH_T_INT: setattr(t, n, int(tab[n]))
+    check(lib().icar_hip_noah_tables(domain.ctx, ctypes.byref(t)), "icar_hip_noah_tables")
+
+
+def _noah_shape(domain, name):
+    return (domain.ny, NOAH_SOIL_LAYERS, domain.nx) if NOAH_ID[name] >= NOAH_ID["soil_water_content"] else (domain.ny, domain.nx)
+
+
+def noah_set(domain, name, values):
+    """icar_hip_noah_upload: one of NOAH_ARRAYS, (ny, nx) -- veg_type / soil_type INTEGER(4) -- or (ny, 4, nx) for the soil arrays"""
+    a = np.ascontiguousarray(values, np.int32 if name in ("veg_type", "soil_type") else np.float32)
+    if a.shape != _noah_shape(domain, name):
+        raise ValueError(f"noah_set {name}: shape {a.shape}, expected {_noah_shape(domain, name)}")
+    check(lib().icar_hip_noah_upload(domain.ctx, NOAH_ID[name], a.ctypes.data_as(ctypes.c_void_p)), f"icar_hip_noah_upload {name}")
+
+
+def noah_get(domain, name):
+    a = np.empty(_noah_shape(domain, name), np.int32 if name in ("veg_type", "soil_type") else np.float32)
+    check(lib().icar_hip_noah_download(domain.ctx, NOAH_ID[name], a.ctypes.data_as(ctypes.c_void_p)), f"icar_hip_noah_download {name}")
+    return a
+
+
+def noah_init(domain, options, fndsnowh=False):
+    """icar_hip_lsm_init: lsm_init with every landsurface that is built.  For kLSM_NOAH the tables (noah_tables) and the domain's
+    arrays (noah_set: veg_type, soil_type, vegfrac, albedo, soil_deep_temperature, soil_water_content, soil_temperature) come first."""
+    o, p = options.lsm_options, options.physics
+    n = noah_options_c(int(o.urban_category), int(o.ice_category), int(o.water_category), int(o.lake_category), int(bool(o.monthly_vegfrac)),
+                       int(bool(o.monthly_albedo)), int(bool(fndsnowh)), float(o.max_swe))
+    check(lib().icar_hip_lsm_init(domain.ctx, int(p.landsurface), int(p.watersurface), int(o.update_interval), float(o.sh_feedback_fraction),
+                                  float(o.lh_feedback_fraction), float(o.sfc_layer_thickness), ctypes.byref(n)), "icar_hip_lsm_init")
+    domain._lsm_key = ((int(p.landsurface), int(p.watersurface)) if int(p.landsurface) == 0 else
+                       (int(p.landsurface), int(p.watersurface), int(o.update_interval), float(o.sh_feedback_fraction), float(o.lh_feedback_fraction),
+                        float(o.sfc_layer_thickness)))
+
+
+def lsm_noah(domain, lsm_dt, its, ite, jts, jte):
+    """icar_hip_lsm_noah: the call of lsm_noah (lsm_driver.f90:1210-1278) alone on a tile"""
+    check(lib().icar_hip_lsm_noah(domain.ctx, float(lsm_dt), int(its), int(ite), int(jts), int(jte)), "icar_hip_lsm_noah")
 
 
 def lsm(domain, options, dt):

@@ -347,7 +347,8 @@ int icar_hip_rad(icar_hip_ctx *ctx, float dt);
  *     %sfc_layer_thickness (400 m); resets last_model_time to its sentinel -999 (:1000) and forgets apply_fluxes' nz.
  *     landsurface: 0 (lsm returns at once, :1014, whatever watersurface is) or 1 = kLSM_BASIC (fluxes prescribed by the host or
  *     computed over open water, applied to the atmosphere).  2 (kLSM_SIMPLE) is refused as the reference refuses it: "Simple LSM
- *     not settup, choose a different LSM options" (:615); 3 (kLSM_NOAH) and 4 (kLSM_NOAHMP) are refused: not built.  watersurface:
+ *     not settup, choose a different LSM options" (:615); 3 (kLSM_NOAH) is refused here ("not built" behind this entry point): it
+ *     needs the tables and options%lsm_options, which icar_hip_lsm_init (L2) takes; 4 (kLSM_NOAHMP) is refused: not built.  watersurface:
  *     0, 1 (kWATER_BASIC: nothing runs, :1038-1050) or ICAR_WATER_SIMPLE = kWATER_SIMPLE; 3 (kWATER_LAKE) is refused: not built.
  *     The values are looked at before the context.  QSFC = water_vapor(:,kms,:) (:568) is taken here when water_vapor is on the
  *     device, else at the first icar_hip_water_simple.  Kept out of icar_hip_step_config so that the struct keeps its layout.
@@ -382,6 +383,114 @@ int icar_hip_water_simple(icar_hip_ctx *ctx);
 int icar_hip_apply_fluxes(icar_hip_ctx *ctx, float dt, int its, int ite, int jts, int jte, int kts, int kte);
 int icar_hip_lsm(icar_hip_ctx *ctx, float dt);
 int icar_hip_lsm_layers(icar_hip_ctx *ctx, int *nz);
+
+/* ---- L2: the Noah land-surface model (src/physics/lsm_noahlsm.f90, src/physics/lsm_noahdrv.f90, src/physics/lsm_driver.f90) -----------
+ * icar_hip_noah_tables: the three tables as SOIL_VEG_GEN_PARM (lsm_noahdrv.f90:1199-1432) parsed them, copied to the device: a host
+ *     calls the reference's own SOIL_VEG_GEN_PARM(LU_Categories, "STAS") and hands module_sf_noahlsm's arrays over, each with the
+ *     module's extent (NLUS = 50, NSLTYPE = 30, NSLOPE = 30); there is no table parser here.  Comes first: the ICAR_NOAH_* arrays
+ *     exist from here on.  Refused before the context: LUCATS / SLCATS / SLPCATS outside the extents, NROTBL outside 0 .. 4, BARE.
+ * icar_hip_lsm_init == lsm_init(domain, options) (lsm_driver.f90:522-711).  landsurface 0, 1, 2: what icar_hip_lsm_configure does
+ *     (noah may be NULL).  ICAR_LSM_NOAH = kLSM_NOAH: the Noah part :619-711.  The domain's arrays it reads must have been uploaded by
+ *     ICAR_NOAH_*: VEG_TYPE, SOIL_TYPE, VEGFRAC (domain%vegetation_fraction(:,1,:)), ALBEDO (domain%albedo(:,1,:)),
+ *     SOIL_DEEP_TEMPERATURE, SOIL_WATER_CONTENT, SOIL_TEMPERATURE (a missing one is an error that names it); SNOW_WATER_EQUIVALENT,
+ *     SNOW_HEIGHT, CANOPY_WATER and LAI are 0 until uploaded, as domain_t allocates them.  It gives the module's own arrays
+ *     allocate_noah_data's values (:425-520: SMSTAV 0.5, SNOALB 0.8, QGH 0.02, ALBBCK 0.17, EMISS 0.99, SHDMIN 0, SHDMAX 100, SH2O 0.25,
+ *     the rest 0; EMBCK = 0.99 is overwritten by SFLX before it is read and has no array), applies the two floors of :674-675
+ *     (SOIL_TEMPERATURE >= 200, SOIL_WATER_CONTENT >= 0.0001), runs LSM_NOAH_INIT's per-cell part (lsm_noahdrv.f90:1095-1188: SNOALB from
+ *     MAXALB, SH2O from FRH2O where the soil is below 273.149 K, SNOW_HEIGHT = 0.005 SNOW_WATER_EQUIVALENT unless fndsnowh -- over the
+ *     WHOLE MEMORY, where the reference takes the tile its .. min(ite, ide-1) of domain%grid (:550-553, :705) and leaves an image's halo
+ *     cells at SH2O = 0.25, SNOALB = 0.8: lsm_noah reads no neighbour, so no owned cell differs) with CANOPY_WATER restored afterwards (:672, :707), sets CQS2 = 0.01 (:708) and LAND_MASK = kLC_WATER where VEG_TYPE
+ *     is water_category or lake_category (:710; a LAND_MASK never uploaded starts as all land).  A cell of the memory whose VEG_TYPE /
+ *     SOIL_TYPE is outside 1 .. LUCATS / 1 .. SLCATS is an error (the reference would read table rows that were never filled), found before
+ *     anything is written: every refusal leaves the context as it was.  New categories or new tables afterwards need a new icar_hip_lsm_init.  The values are looked at before the context: 4 (kLSM_NOAHMP) and
+ *     watersurface = 3 (kWATER_LAKE) are refused: not built; monthly_vegfrac / monthly_albedo are refused: not built (the host uploads
+ *     the month's VEGFRAC / ALBEDO itself).
+ * icar_hip_lsm_noah == `call lsm_noah(...)` (lsm_driver.f90:1210-1278; lsm_noahdrv.f90:36-1018 with SFLX and its 27 helpers,
+ *     lsm_noahlsm.f90:64-4228) alone on its..ite, jts..jte with DT = lsm_dt and the constants of allocate_noah_data (four soil layers of
+ *     0.1, 0.3, 0.6, 1.0 m, ITIMESTEP = 1, XICE = 0, MYJ / FRPCPN / RDLAI2D / USEMONALB / UA_PHYS false): from WATER_VAPOR, TEMPERATURE (level 1),
+ *     PRESSURE_INTERFACE (levels 1, 2), SHORTWAVE, LONGWAVE, LAND_MASK, the ICAR_NOAH_* inputs and state -> SKIN_TEMPERATURE, SENSIBLE_HEAT,
+ *     LATENT_HEAT, QFX, QSFC, ROUGHNESS_Z0 (ZNT) and the ICAR_NOAH_* state.  RAINBL is ICAR_NOAH_CURRENT_PRECIPITATION, CHS ICAR_NOAH_CHS, Ri
+ *     ICAR_NOAH_RI, QGH ICAR_NOAH_QGH: the statements of lsm() that make them (:1028-1030, :1181-1187, :1207) are NOT built, the host uploads
+ *     them (CHS is required; the others keep lsm_init's values).  Bit-identical to the compiled reference in every cell that runs SFLX
+ *     and every water cell (the every-call block lsm_noahdrv.f90:623-650).  A land-ice cell (VEG_TYPE == ice_category, :887-901) gets
+ *     what the reference defines there (SOIL_WATER_CONTENT = SH2O = SMCREL = 1, LAI = 0.01, SOIL_TOTALMOISTURE = 0, the re-derived snow
+ *     height, ...); ALBEDO, ZNT, the fluxes, QSFC, POTEVP, NOAHRES, SMSTAV, SFCRUNOFF, ACSNOM, SNOPCX and FLX4 / FVB / FBUR / FGSN are
+ *     left as they are: the reference stores locals there that only SFLX sets, i.e. the values of the cell visited before.  Refused:
+ *     kts /= 1 or a single level (lsm_noah names level 1 literally), a tile outside the memory.
+ * icar_hip_lsm (L1) with Noah initialised answers that the Noah branch of lsm() is not built and names icar_hip_lsm_noah; icar_hip_substep /
+ *     _step / _step_n answer the same before they issue anything.
+ * icar_hip_noah_upload / _download: the arrays by ICAR_NOAH_*: (nx,ny) REAL(4), but VEG_TYPE / SOIL_TYPE INTEGER(4) (nx,ny) and the four
+ *     soil arrays REAL(4) (nx,4,ny). */
+enum { ICAR_LSM_NOAH = 3 };
+enum icar_hip_noah_array {
+    ICAR_NOAH_VEG_TYPE = 0,                /* domain%veg_type   INTEGER(4)                                        */
+    ICAR_NOAH_SOIL_TYPE = 1,               /* domain%soil_type  INTEGER(4)                                        */
+    ICAR_NOAH_VEGFRAC = 2,                 /* lsm_driver.f90's VEGFRAC [%]                                         */
+    ICAR_NOAH_SOIL_DEEP_TEMPERATURE = 3,   /* domain%soil_deep_temperature%data_2d (TMN)                           */
+    ICAR_NOAH_SHDMIN = 4,                  /* the module's own arrays, named as lsm_driver.f90 names them          */
+    ICAR_NOAH_SHDMAX = 5,
+    ICAR_NOAH_SNOALB = 6,
+    ICAR_NOAH_QGH = 7,
+    ICAR_NOAH_CHS = 8,
+    ICAR_NOAH_CQS2 = 9,
+    ICAR_NOAH_RI = 10,
+    ICAR_NOAH_CURRENT_PRECIPITATION = 11,  /* current_precipitation (:1207) [kg m-2 per lsm_dt]                    */
+    ICAR_NOAH_GROUND_HEAT_FLUX = 12,       /* domain%ground_heat_flux%data_2d                                      */
+    ICAR_NOAH_SMSTAV = 13,
+    ICAR_NOAH_SOIL_TOTALMOISTURE = 14,     /* domain%soil_totalmoisture%data_2d (SMSTOT)                           */
+    ICAR_NOAH_SFCRUNOFF = 15,
+    ICAR_NOAH_UDRUNOFF = 16,
+    ICAR_NOAH_ALBEDO = 17,
+    ICAR_NOAH_ALBBCK = 18,
+    ICAR_NOAH_Z0 = 19,
+    ICAR_NOAH_EMISS = 20,
+    ICAR_NOAH_SNOWC = 21,
+    ICAR_NOAH_SNOW_WATER_EQUIVALENT = 22,  /* domain%snow_water_equivalent%data_2d [kg m-2]                        */
+    ICAR_NOAH_SNOW_HEIGHT = 23,            /* domain%snow_height%data_2d [m]                                       */
+    ICAR_NOAH_CANOPY_WATER = 24,           /* domain%canopy_water%data_2d                                          */
+    ICAR_NOAH_CHS2 = 25,
+    ICAR_NOAH_CHKLOWQ = 26,
+    ICAR_NOAH_LAI = 27,                    /* domain%lai%data_2d                                                   */
+    ICAR_NOAH_SNOTIME = 28,
+    ICAR_NOAH_ACSNOM = 29,
+    ICAR_NOAH_ACSNOW = 30,
+    ICAR_NOAH_SNOPCX = 31,
+    ICAR_NOAH_POTEVP = 32,
+    ICAR_NOAH_NOAHRES = 33,
+    ICAR_NOAH_FLX4 = 34,
+    ICAR_NOAH_FVB = 35,
+    ICAR_NOAH_FBUR = 36,
+    ICAR_NOAH_FGSN = 37,
+    ICAR_NOAH_SOIL_WATER_CONTENT = 38,     /* domain%soil_water_content%data_3d (nx,4,ny) (SMOIS)                  */
+    ICAR_NOAH_SOIL_TEMPERATURE = 39,       /* domain%soil_temperature%data_3d (nx,4,ny) (TSLB)                     */
+    ICAR_NOAH_SH2O = 40,                   /* (nx,4,ny)                                                            */
+    ICAR_NOAH_SMCREL = 41,                 /* (nx,4,ny)                                                            */
+    ICAR_NOAH_N = 42
+};
+/* module_sf_noahlsm's public table variables (lsm_noahlsm.f90:26-54); arrays of NLUS = 50, NSLTYPE = 30, NSLOPE = 30 elements */
+typedef struct icar_hip_noah_tables_t {
+    const int *nrotbl;
+    const float *snuptbl, *rstbl, *rgltbl, *hstbl, *maxalb, *emissmintbl, *emissmaxtbl, *laimintbl, *laimaxtbl, *z0mintbl, *z0maxtbl,
+        *albedomintbl, *albedomaxtbl;
+    const float *bb, *drysmc, *f11, *maxsmc, *refsmc, *satpsi, *satdk, *satdw, *wltsmc, *qtz;
+    const float *slope_data;
+    float topt_data, cmcmax_data, cfactr_data, rsmax_data;
+    float sbeta_data, fxexp_data, csoil_data, salp_data, refdk_data, refkdt_data, frzk_data, zbot_data, lvcoef_data;
+    int bare, lucats, slcats, slpcats;
+} icar_hip_noah_tables_t;
+/* options%lsm_options as lsm_init reads them for Noah (lsm_driver.f90:633-651, :1280) */
+typedef struct icar_hip_noah_options_t {
+    int urban_category, ice_category, water_category, lake_category;
+    int monthly_vegfrac, monthly_albedo;      /* must be 0: not built */
+    int fndsnowh;                             /* FNDSNOWH (:633-642): 1 = SNOW_HEIGHT was read from the input, 0 = derive it from the snow water */
+    float max_swe;
+} icar_hip_noah_options_t;
+int icar_hip_noah_tables(icar_hip_ctx *ctx, const icar_hip_noah_tables_t *tables);
+int icar_hip_lsm_init(icar_hip_ctx *ctx, int landsurface, int watersurface, int update_interval, float sh_feedback_fraction,
+                      float lh_feedback_fraction, float sfc_layer_thickness, const icar_hip_noah_options_t *noah);
+int icar_hip_lsm_noah(icar_hip_ctx *ctx, float lsm_dt, int its, int ite, int jts, int jte);
+int icar_hip_noah_upload(icar_hip_ctx *ctx, int which, const void *host);
+int icar_hip_noah_download(icar_hip_ctx *ctx, int which, void *host);
 
 /* ---- C1: the convection slot (src/physics/cu_driver.f90 with convection = kCU_BMJ, src/physics/cu_bmj.f90) ---------------------------
  * icar_hip_cu_configure: init_convection (cu_driver.f90:97-253) -- options%physics%convection and options%cu_options.
