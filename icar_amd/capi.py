@@ -35,6 +35,7 @@ SYMBOLS = [
     "icar_hip_ra_simple", "icar_hip_rad_configure", "icar_hip_rad_calendar", "icar_hip_rad",
     "icar_hip_lsm_configure", "icar_hip_diag_10m", "icar_hip_water_simple", "icar_hip_apply_fluxes", "icar_hip_lsm", "icar_hip_lsm_layers",
     "icar_hip_noah_tables", "icar_hip_lsm_init", "icar_hip_lsm_noah", "icar_hip_noah_upload", "icar_hip_noah_download",
+    "icar_hip_lsm_noah_couple", "icar_hip_lsm_upload", "icar_hip_lsm_download",
     "icar_hip_cu_configure", "icar_hip_cu_bmj", "icar_hip_convect", "icar_hip_cu_reset", "icar_hip_cu_upload", "icar_hip_cu_download", "icar_hip_cu_tables",
     "icar_hip_cu_init", "icar_hip_cu_tiedtke", "icar_hip_tiedtke_upload", "icar_hip_tiedtke_download",
     "icar_hip_convection_init", "icar_hip_cu_nsas", "icar_hip_nsas_upload", "icar_hip_nsas_download",
@@ -158,6 +159,9 @@ def lib():
         L.icar_hip_lsm_noah.argtypes = [vp, cf, ci, ci, ci, ci]
         L.icar_hip_noah_upload.argtypes = [vp, ci, vp]
         L.icar_hip_noah_download.argtypes = [vp, ci, vp]
+        L.icar_hip_lsm_noah_couple.argtypes = [vp]
+        L.icar_hip_lsm_upload.argtypes = [vp, ci, vp]
+        L.icar_hip_lsm_download.argtypes = [vp, ci, vp]
         L.icar_hip_cu_configure.argtypes = [vp, ci, cf, cf, cf, cf, cf, cf]
         L.icar_hip_cu_bmj.argtypes = [vp, cf, ci, ci, ci, ci]
         L.icar_hip_convect.argtypes = [vp, cf]

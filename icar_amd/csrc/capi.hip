@@ -153,6 +153,7 @@ int icar_hip_ctx_destroy(icar_hip_ctx *c)
     if (c->sfc_levelmax) hipFree(c->sfc_levelmax);
     icar_cu_free(c);
     icar_noah_free(c);
+    icar_lsm_driver_free(c);
     icar_ysu_free(c);
     icar_wsm3_free(c);
     icar_wsm6_free(c);

@@ -30,6 +30,7 @@ struct CuState;          // cu_bmj.hip
 struct YsuState;         // pbl_ysu.hip
 struct ForcingState;     // forcing.hip
 struct NoahState;        // lsm_noah.hip
+struct LsmDriverState;   // lsm_noah_driver.hip
 
 // state of the step driver (timestep.hip): the options / grid members the sub-step loop reads, the model clock, and what
 // mp_driver.f90 keeps in SAVE variables (last_model_time)
@@ -113,6 +114,7 @@ struct icar_hip_ctx {
     unsigned *sfc_levelmax = nullptr;
     CuState *cu = nullptr;               // cu_bmj.hip: the convection slot's arrays, BMJINIT's tables and the column workspace
     NoahState *noah = nullptr;           // lsm_noah.hip: the Noah tables and the model's own arrays (ICAR_NOAH_*)
+    LsmDriverState *lsmdrv = nullptr;    // lsm_noah_driver.hip: the ICAR_LSM_* arrays and whether icar_hip_lsm_noah_couple has run since lsm_init
     YsuState *ysu = nullptr;             // pbl_ysu.hip: pbl_init's arrays, the scheme's results and tendencies, the column workspace
     // reductions / flags
     float *d_red = nullptr;              // small device scratch for reductions
@@ -191,6 +193,15 @@ int icar_lsm_run(icar_hip_ctx *c, float dt);                                // l
 int icar_lsm_init_device(icar_hip_ctx *c);
 // lsm_noah.hip
 void icar_noah_free(icar_hip_ctx *c);
+bool icar_noah_ready(const icar_hip_ctx *c);                                // tables on the device and icar_hip_lsm_init run since the last tables / categories
+float *icar_noah_array(icar_hip_ctx *c, int which);                         // an ICAR_NOAH_* array (icar_noah_ready)
+float icar_noah_max_swe(const icar_hip_ctx *c);
+int icar_noah_run(icar_hip_ctx *c, bool chs_from_host, float lsm_dt, int its, int ite, int jts, int jte);   // the call of lsm_noah
+// lsm_noah_driver.hip
+void icar_lsm_driver_free(icar_hip_ctx *c);
+void icar_lsm_uncouple(icar_hip_ctx *c);                                    // a new lsm_init / lsm_configure: lsm() refuses Noah again
+bool icar_lsm_noah_coupled(const icar_hip_ctx *c);                          // icar_hip_lsm_noah_couple has run and Noah is still initialised
+int icar_lsm_noah_gated_run(icar_hip_ctx *c, float lsm_dt);                 // the gated block of lsm() for kLSM_NOAH (lsm_driver.f90:1028-1546)
 // cu_bmj.hip
 void icar_cu_free(icar_hip_ctx *c);
 int icar_cu_init_device(icar_hip_ctx *c);                                   // init_convection for kCU_BMJ: arrays, tables, workspace

@@ -398,6 +398,7 @@ extern "C" int icar_hip_lsm_init(icar_hip_ctx *c, int landsurface, int watersurf
     HIPCHK(hipStreamSynchronize(c->stream));
     s->opt = *o;
     s->initialised = true;
+    icar_lsm_uncouple(c);                                                          // icar_hip_lsm_noah_couple comes after this call
     IcarStepState &st = c->step;
     st.landsurface = landsurface; st.watersurface = watersurface; st.lsm_update_interval = update_interval;
     st.sh_feedback_fraction = sh_feedback_fraction; st.lh_feedback_fraction = lh_feedback_fraction; st.sfc_layer_thickness = sfc_layer_thickness;
@@ -406,15 +407,26 @@ extern "C" int icar_hip_lsm_init(icar_hip_ctx *c, int landsurface, int watersurf
     return 0;
 }
 
+// what lsm_noah_driver.hip needs of the state above
+bool icar_noah_ready(const icar_hip_ctx *c) { return c->noah && c->noah->tables && c->noah->initialised; }
+float *icar_noah_array(icar_hip_ctx *c, int w) { return c->noah->arr[w]; }
+float icar_noah_max_swe(const icar_hip_ctx *c) { return c->noah->opt.max_swe; }
+
 // the call of lsm_noah alone (lsm_driver.f90:1210-1278) on its..ite, jts..jte with RAINBL = ICAR_NOAH_CURRENT_PRECIPITATION
 extern "C" int icar_hip_lsm_noah(icar_hip_ctx *c, float lsm_dt, int its, int ite, int jts, int jte)
 {
     if (!(lsm_dt > 0)) { icar_set_error("lsm_noah: lsm_dt is positive (PRCP = RAINBL / DT, lsm_noahdrv.f90:692)"); return 1; }
     if (icar_enter(c, "lsm_noah")) return 1;
+    return icar_noah_run(c, true, lsm_dt, its, ite, jts, jte);
+}
+
+// chs_from_host: CHS is the host's (icar_hip_lsm_noah); false: the coupled lsm() has just computed it (lsm_noah_driver.hip)
+int icar_noah_run(icar_hip_ctx *c, bool chs_from_host, float lsm_dt, int its, int ite, int jts, int jte)
+{
     NoahState *s = state(c, "lsm_noah");
     if (!s) return 1;
     if (!s->initialised) { icar_set_error("lsm_noah: the scheme is not initialised (icar_hip_lsm_init with landsurface = 3, again after new veg_type / soil_type or new tables)"); return 1; }
-    if (!s->uploaded[ICAR_NOAH_CHS]) {
+    if (chs_from_host && !s->uploaded[ICAR_NOAH_CHS]) {
         icar_set_error("lsm_noah: CHS (ICAR_NOAH_CHS) is not on the device: calc_exchange_coefficient (lsm_driver.f90:1028-1030) is not built, the host "
                        "uploads its result before the call");
         return 1;

@@ -337,7 +337,8 @@ int icar_lsm_run(icar_hip_ctx *c, float dt)
 {
     IcarStepState &s = c->step;
     if (s.landsurface == 0) return 0;                                 // :1014, whatever watersurface is
-    if (s.landsurface == ICAR_LSM_NOAH) {
+    const bool noah = s.landsurface == ICAR_LSM_NOAH;
+    if (noah && !icar_lsm_noah_coupled(c)) {                          // (coupled: icar_hip_lsm_noah_couple, lsm_noah_driver.hip)
         icar_set_error("lsm: the Noah branch of lsm() (lsm_driver.f90:1177-1291: CHS, QGH, current_precipitation, the statements after the call, "
                        "soil_totalmoisture, surface_diagnostics) is not built: Noah runs through icar_hip_lsm_noah only");
         return 1;
@@ -345,8 +346,11 @@ int icar_lsm_run(icar_hip_ctx *c, float dt)
     const double now = s.model_time, upd = (double)s.lsm_update_interval;
     if (s.lsm_last_model_time == -999.0) s.lsm_last_model_time = now - upd;                          // :1016-1018
     if ((now - s.lsm_last_model_time) >= upd) {                                                      // :1021
+        const float lsm_dt = (float)(now - s.lsm_last_model_time);                                   // :1022
+        if (noah && !(lsm_dt > 0)) { icar_set_error("lsm: lsm_dt = 0 (update_interval = 0 at the first call): lsm_noah divides by it (PRCP = RAINBL / DT, lsm_noahdrv.f90:692)"); return 1; }
         s.lsm_last_model_time = now;                                                                 // :1023
-        if (s.watersurface == ICAR_WATER_SIMPLE && icar_sfc_water_simple_run(c)) return 1;           // :1051-1073
+        if (noah) { if (icar_lsm_noah_gated_run(c, lsm_dt)) return 1; }                              // :1028-1546, water_simple inside
+        else if (s.watersurface == ICAR_WATER_SIMPLE && icar_sfc_water_simple_run(c)) return 1;           // :1051-1073
     }
     const icar_hip_step_config &g = s.cfg;
     return icar_sfc_apply_fluxes_run(c, dt, g.its, g.ite, g.jts, g.jte, g.kts, g.kte);               // :1550-1552

@@ -52,7 +52,7 @@ static bool cfg_ok(icar_hip_ctx *c, const char *who)
 // found that out in its lsm slot would have run diagnostic_update and rad already
 static bool lsm_slot_ok(icar_hip_ctx *c, const char *who)
 {
-    if (c->step.landsurface != ICAR_LSM_NOAH) return true;
+    if (c->step.landsurface != ICAR_LSM_NOAH || icar_lsm_noah_coupled(c)) return true;      // (coupled: icar_hip_lsm_noah_couple)
     icar_set_error(std::string(who) + ": landsurface = 3 (kLSM_NOAH): the Noah branch of lsm() (lsm_driver.f90:1177-1291) is not built, so the step's lsm slot "
                    "cannot run: Noah runs through icar_hip_lsm_noah only");
     return false;
@@ -637,6 +637,7 @@ int icar_hip_lsm_configure(icar_hip_ctx *c, int landsurface, int watersurface, i
     s.sh_feedback_fraction = sh_feedback_fraction; s.lh_feedback_fraction = lh_feedback_fraction; s.sfc_layer_thickness = sfc_layer_thickness;
     s.lsm_last_model_time = -999.0;                                               // lsm_driver.f90:1000
     c->sfc_nz_valid = false;                                                      // apply_fluxes' SAVE variable nz
+    icar_lsm_uncouple(c);
     HIPCHK(hipSetDevice(c->device));
     return icar_lsm_init_device(c);
 }

@@ -29,6 +29,9 @@ module icar_hip
             hip_lsm_configure, hip_diag_10m, hip_water_simple, hip_apply_fluxes, hip_lsm, hip_lsm_layers, ICAR_LSM_BASIC, ICAR_WATER_SIMPLE, &
             hip_noah_tables_t, hip_noah_options_t, hip_noah_tables, hip_lsm_init, hip_lsm_noah, hip_noah_upload, hip_noah_upload_int, hip_noah_download, &
             hip_noah_download_int, ICAR_LSM_NOAH, &
+            hip_lsm_noah_couple, hip_lsm_upload, hip_lsm_upload_r8, hip_lsm_download, hip_lsm_download_r8, &
+            ICAR_LSM_TEMPERATURE_2M, ICAR_LSM_HUMIDITY_2M, ICAR_LSM_LONGWAVE_UP, ICAR_LSM_RAINBL, ICAR_LSM_Z_ATM, ICAR_LSM_LNZ_ATM_TERM, &
+            ICAR_LSM_BASE_EXCHANGE_TERM, ICAR_LSM_N, &
             ICAR_NOAH_VEG_TYPE, ICAR_NOAH_SOIL_TYPE, ICAR_NOAH_VEGFRAC, ICAR_NOAH_SOIL_DEEP_TEMPERATURE, ICAR_NOAH_SHDMIN, ICAR_NOAH_SHDMAX, &
             ICAR_NOAH_SNOALB, ICAR_NOAH_QGH, ICAR_NOAH_CHS, ICAR_NOAH_CQS2, ICAR_NOAH_RI, ICAR_NOAH_CURRENT_PRECIPITATION, &
             ICAR_NOAH_GROUND_HEAT_FLUX, ICAR_NOAH_SMSTAV, ICAR_NOAH_SOIL_TOTALMOISTURE, ICAR_NOAH_SFCRUNOFF, ICAR_NOAH_UDRUNOFF, ICAR_NOAH_ALBEDO, &
@@ -105,6 +108,11 @@ module icar_hip
        ICAR_NOAH_ACSNOM=29, ICAR_NOAH_ACSNOW=30, ICAR_NOAH_SNOPCX=31, ICAR_NOAH_POTEVP=32, ICAR_NOAH_NOAHRES=33, ICAR_NOAH_FLX4=34, ICAR_NOAH_FVB=35, &
        ICAR_NOAH_FBUR=36, ICAR_NOAH_FGSN=37, ICAR_NOAH_SOIL_WATER_CONTENT=38, ICAR_NOAH_SOIL_TEMPERATURE=39, ICAR_NOAH_SH2O=40, ICAR_NOAH_SMCREL=41, &
        ICAR_NOAH_N=42
+  ! enum icar_hip_lsm_array (include/icar_hip.h): what the Noah branch of lsm() keeps beside the ICAR_NOAH_* arrays, REAL(4) (nx,ny) but
+  ! RAINBL, which is REAL(8)
+  integer(c_int), parameter :: &
+       ICAR_LSM_TEMPERATURE_2M=0, ICAR_LSM_HUMIDITY_2M=1, ICAR_LSM_LONGWAVE_UP=2, ICAR_LSM_RAINBL=3, ICAR_LSM_Z_ATM=4, ICAR_LSM_LNZ_ATM_TERM=5, &
+       ICAR_LSM_BASE_EXCHANGE_TERM=6, ICAR_LSM_N=7
   real(c_float), parameter :: ICAR_CU_NO_STOCHASTIC = -9999.0   ! kNO_STOCHASTIC, icar_constants.f90:340
   ! enum icar_hip_cu_array (include/icar_hip.h): the convection slot's own arrays, REAL(4) (nx,ny) but for the two tendencies (nx,nz,ny)
   integer(c_int), parameter :: ICAR_CU_CLDEFI=0, ICAR_CU_ACC_CONV_PCP=1, ICAR_CU_RAINCV=2, ICAR_CU_CUTOP=3, ICAR_CU_CUBOT=4, &
@@ -306,6 +314,15 @@ module icar_hip
        import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
      end function
      integer(c_int) function icar_hip_noah_download(ctx, which, host) bind(C, name="icar_hip_noah_download")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
+     end function
+     integer(c_int) function icar_hip_lsm_noah_couple(ctx) bind(C, name="icar_hip_lsm_noah_couple")
+       import; type(c_ptr), value :: ctx
+     end function
+     integer(c_int) function icar_hip_lsm_upload(ctx, which, host) bind(C, name="icar_hip_lsm_upload")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
+     end function
+     integer(c_int) function icar_hip_lsm_download(ctx, which, host) bind(C, name="icar_hip_lsm_download")
        import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which
      end function
      integer(c_int) function icar_hip_cu_configure(ctx, convection, stochastic_cu, tendency_fraction, tend_qv_fraction, tend_qc_fraction, &
@@ -814,6 +831,42 @@ contains
     integer(c_int), intent(in) :: which
     integer(c_int), intent(inout), target, contiguous :: a(:,:)
     call check(icar_hip_noah_download(ctx%p, which, c_loc(a)), "noah_download")
+  end subroutine
+
+  !> what lsm_init does for Noah beside hip_lsm_init's part (lsm_driver.f90:566, :583-587, :592-596, :602-603, :610-611, :992-997), after
+  !! hip_lsm_init(.., ICAR_LSM_NOAH, ..): from here on hip_lsm and the step entry points run the Noah branch of lsm() (:1028-1546)
+  subroutine hip_lsm_noah_couple(ctx)
+    type(hip_ctx_t), intent(in) :: ctx
+    call check(icar_hip_lsm_noah_couple(ctx%p), "lsm_noah_couple")
+  end subroutine
+
+  !> the arrays of that branch by ICAR_LSM_*: REAL(4) (nx,ny); ICAR_LSM_RAINBL, REAL(8), through the _r8 pair
+  subroutine hip_lsm_upload(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(in), target, contiguous :: a(:,:)
+    call check(icar_hip_lsm_upload(ctx%p, which, c_loc(a)), "lsm_upload")
+  end subroutine
+
+  subroutine hip_lsm_upload_r8(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_double), intent(in), target, contiguous :: a(:,:)
+    call check(icar_hip_lsm_upload(ctx%p, which, c_loc(a)), "lsm_upload")
+  end subroutine
+
+  subroutine hip_lsm_download(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(inout), target, contiguous :: a(:,:)
+    call check(icar_hip_lsm_download(ctx%p, which, c_loc(a)), "lsm_download")
+  end subroutine
+
+  subroutine hip_lsm_download_r8(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_double), intent(inout), target, contiguous :: a(:,:)
+    call check(icar_hip_lsm_download(ctx%p, which, c_loc(a)), "lsm_download")
   end subroutine
 
   !> init_convection (cu_driver.f90:97-253): options%physics%convection (0 or ICAR_CU_BMJ; Tiedtke goes through hip_cu_init, NSAS through hip_convection_init, 2 and 3 have no

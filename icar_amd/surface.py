@@ -5,7 +5,8 @@ landsurface = kLSM_BASIC (fluxes prescribed by the host or the forcing and appli
 kWATER_BASIC (nothing runs) or kWATER_SIMPLE (src/physics/water_simple.f90: bulk fluxes over open water) is built whole; kLSM_SIMPLE stops
 in the reference's own lsm_init and is refused with its message, Noah-MP and the lake model are refused by the library.  Of
 kLSM_NOAH lsm_init's part and the call of lsm_noah are built (noah_tables, noah_init, lsm_noah, noah_set / noah_get); the rest of the
-Noah branch of lsm() is not, and lsm() says so."""
+Noah branch of lsm() runs once noah_couple has been called behind noah_init (lsm_set / lsm_get hold its arrays); without that call
+lsm() says that Noah runs through lsm_noah only."""
 import ctypes
 
 import numpy as np
@@ -20,6 +21,9 @@ NOAH_ARRAYS = ["veg_type", "soil_type", "vegfrac", "soil_deep_temperature", "shd
                "potevp", "noahres", "flx4", "fvb", "fbur", "fgsn", "soil_water_content", "soil_temperature", "sh2o", "smcrel"]
 NOAH_ID = {n: i for i, n in enumerate(NOAH_ARRAYS)}
 NOAH_SOIL_LAYERS = 4
+# enum icar_hip_lsm_array (include/icar_hip.h): (ny, nx) REAL(4), rainbl REAL(8)
+LSM_ARRAYS = ["temperature_2m", "humidity_2m", "longwave_up", "rainbl", "z_atm", "lnz_atm_term", "base_exchange_term"]
+LSM_ID = {n: i for i, n in enumerate(LSM_ARRAYS)}
 
 
 def lsm_var_request(options):
@@ -96,9 +100,30 @@ def lsm_noah(domain, lsm_dt, its, ite, jts, jte):
     check(lib().icar_hip_lsm_noah(domain.ctx, float(lsm_dt), int(its), int(ite), int(jts), int(jte)), "icar_hip_lsm_noah")
 
 
+def noah_couple(domain):
+    """icar_hip_lsm_noah_couple: the rest of lsm_init for Noah (lsm_driver.f90:566, :583-611, :992-997), after noah_init; from here on
+    lsm() and the step run the Noah branch of lsm() on the device"""
+    check(lib().icar_hip_lsm_noah_couple(domain.ctx), "icar_hip_lsm_noah_couple")
+
+
+def lsm_set(domain, name, values):
+    """icar_hip_lsm_upload: one of LSM_ARRAYS, (ny, nx)"""
+    a = np.ascontiguousarray(values, np.float64 if name == "rainbl" else np.float32)
+    if a.shape != (domain.ny, domain.nx):
+        raise ValueError(f"lsm_set {name}: shape {a.shape}, expected {(domain.ny, domain.nx)}")
+    check(lib().icar_hip_lsm_upload(domain.ctx, LSM_ID[name], a.ctypes.data_as(ctypes.c_void_p)), f"icar_hip_lsm_upload {name}")
+
+
+def lsm_get(domain, name):
+    a = np.empty((domain.ny, domain.nx), np.float64 if name == "rainbl" else np.float32)
+    check(lib().icar_hip_lsm_download(domain.ctx, LSM_ID[name], a.ctypes.data_as(ctypes.c_void_p)), f"icar_hip_lsm_download {name}")
+    return a
+
+
 def lsm(domain, options, dt):
     """lsm(domain, options, dt) (lsm_driver.f90:1005-1554) on the tile its..kte of the domain's grid at the model clock: the update
-    gate, water_simple inside it, apply_fluxes every call; dt a REAL(4) like real(dt%seconds())."""
+    gate, water_simple inside it (and, with Noah coupled by noah_couple, the whole Noah branch), apply_fluxes every call; dt a REAL(4)
+    like real(dt%seconds())."""
     if options.physics.landsurface == 0:
         return
     domain.configure(options)

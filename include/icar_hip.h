@@ -492,6 +492,49 @@ int icar_hip_lsm_noah(icar_hip_ctx *ctx, float lsm_dt, int its, int ite, int jts
 int icar_hip_noah_upload(icar_hip_ctx *ctx, int which, const void *host);
 int icar_hip_noah_download(icar_hip_ctx *ctx, int which, void *host);
 
+/* ---- L3: the Noah branch of lsm() around the call (src/physics/lsm_driver.f90 with landsurface = kLSM_NOAH) ------------------------------
+ * Nothing below changes what L1 and L2 do until icar_hip_lsm_noah_couple has been called.
+ * icar_hip_lsm_noah_couple == what lsm_init does for Noah beside the part of icar_hip_lsm_init, called after
+ *     icar_hip_lsm_init(.., ICAR_LSM_NOAH, ..): Z0 = roughness_z0 (lsm_driver.f90:566, into ICAR_NOAH_Z0), current_precipitation = 0
+ *     (:583-587; windspd = 3 is overwritten at :1028 before anything reads it and has no array), CHS = 0.01 and CHS2 = 0.01 (:592-596),
+ *     RAINBL = accumulated_precipitation (:602-603, REAL(8)), temperature_2m = temperature(:,kms,:) and humidity_2m = water_vapor(:,kms,:)
+ *     (:610-611), z_atm = z(:,kts,:) - terrain (:992), lnz_atm_term and base_exchange_term (:993-997) with exchange_term = 1.  That is the
+ *     only value lsm_init ever sets (:535): calc_mahrt_holtslag_exchange_coefficient and F2_formula (:269-297) are unreachable and are NOT
+ *     built.  Needs ROUGHNESS_Z0, Z, TERRAIN, TEMPERATURE, WATER_VAPOR, SURFACE_PRESSURE and either U_10M / V_10M or U_MASS / V_MASS (then
+ *     icar_hip_diag_10m runs once); a missing one is an error that names it.  ICAR_F_PRECIPITATION never uploaded is the zeros domain_t
+ *     allocates.  Refused before anything is written, the context left as it was: Noah not initialised (or new tables / categories / another
+ *     icar_hip_lsm_init or _lsm_configure since), a step tile with kts /= kms.  A later icar_hip_lsm_init / icar_hip_lsm_configure drops the
+ *     coupling: icar_hip_lsm and the step entry points refuse Noah again until the next icar_hip_lsm_noah_couple.
+ * icar_hip_lsm (L1) with the coupling made == lsm(domain, options, dt) for kLSM_NOAH (:1005-1554): the gate on the library clock
+ *     (:1016-1023, lsm_dt the REAL(8) difference stored into a REAL(4)); inside it windspd (:1028) and calc_exchange_coefficient (:244-265)
+ *     over the memory rectangle into ICAR_NOAH_RI / ICAR_NOAH_CHS; water_simple when watersurface = 2 (:1051-1073); windspd floored at 1,
+ *     CHS = CHS * windspd, CHS2 = CHS, CQS2 = CHS (:1144-1147); QGH = sat_mr(temperature_2m, surface_pressure) where land_mask == kLC_LAND
+ *     (:1181-1187, sat_mr of atm_utilities.f90:523-560); current_precipitation = accumulated_precipitation - RAINBL (:1207, a REAL(8)
+ *     difference rounded to REAL(4); domain%rain_fraction, :1208, is allocated only with the bias-correction options, is NOT built and cannot
+ *     be supplied); lsm_noah (:1210-1278) on the tile of icar_hip_step_configure; then over the memory rectangle the max_swe clamp (:1280),
+ *     the exchange terms from the new roughness_z0 (:1282-1286), longwave_up (:1289), RAINBL = accumulated_precipitation (:1290; rain_bucket,
+ *     :1291, feeds only a commented-out term and has no array); soil_totalmoisture (:1524-1527, which overwrites what lsm_noah stored, land-ice
+ *     cells included); surface_diagnostics (:299-359) on its..ite, jts..jte.  Of surface_diagnostics only the bulk arm (:337-352) is built: for
+ *     Noah lsm_var_request (:119-129) allocates temperature_2m_veg but not temperature_2m_bare, so `associated(T2bare)` is false and the veg
+ *     and bare arms are dead.  Then, every call, icar_hip_apply_fluxes (:1550-1552).  The host uploads neither CHS, Ri, QGH nor
+ *     current_precipitation and keeps none of these statements.  icar_hip_substep / _step / _step_n run this in their lsm slot
+ *     (time_step.f90:491).
+ * icar_hip_lsm_upload / _download: the arrays of enum icar_hip_lsm_array, (nx,ny) REAL(4) but RAINBL REAL(8) -- what a restart hands over
+ *     beside the ICAR_NOAH_* arrays (upload them after icar_hip_lsm_noah_couple, which rewrites all but LONGWAVE_UP). */
+enum icar_hip_lsm_array {
+    ICAR_LSM_TEMPERATURE_2M = 0,           /* domain%temperature_2m%data_2d                                        */
+    ICAR_LSM_HUMIDITY_2M = 1,              /* domain%humidity_2m%data_2d                                           */
+    ICAR_LSM_LONGWAVE_UP = 2,              /* domain%longwave_up%data_2d                                           */
+    ICAR_LSM_RAINBL = 3,                   /* lsm_driver.f90's RAINBL  REAL(8)                                     */
+    ICAR_LSM_Z_ATM = 4,
+    ICAR_LSM_LNZ_ATM_TERM = 5,
+    ICAR_LSM_BASE_EXCHANGE_TERM = 6,
+    ICAR_LSM_N = 7
+};
+int icar_hip_lsm_noah_couple(icar_hip_ctx *ctx);
+int icar_hip_lsm_upload(icar_hip_ctx *ctx, int which, const void *host);
+int icar_hip_lsm_download(icar_hip_ctx *ctx, int which, void *host);
+
 /* ---- C1: the convection slot (src/physics/cu_driver.f90 with convection = kCU_BMJ, src/physics/cu_bmj.f90) ---------------------------
  * icar_hip_cu_configure: init_convection (cu_driver.f90:97-253) -- options%physics%convection and options%cu_options.
  *     convection: 0 (convect returns at once, :264) or ICAR_CU_BMJ = kCU_BMJ (icar_constants.f90:345).  1 (kCU_TIEDTKE) is refused here:
