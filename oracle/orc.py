@@ -120,6 +120,33 @@ def thompson(qv, qc, qr, qi, qs, qg, ni, nr, th, pii, p, dz, dt, rainnc, rainncv
                        *[_i(x) for x in (ids, ide, jds, jde, kds, kde, its, ite, jts, jte, kts, kte)])
 
 
+THOMPSON_TABLES = ["tcg_racg", "tmr_racg", "tcr_gacr", "tmg_gacr", "tnr_racg", "tnr_gacr", "tcs_racs1", "tmr_racs1", "tcs_racs2", "tmr_racs2",
+                   "tcr_sacr1", "tms_sacr1", "tcr_sacr2", "tms_sacr2", "tnr_racs1", "tnr_racs2", "tnr_sacr1", "tnr_sacr2", "tpi_qcfz", "tni_qcfz",
+                   "tpi_qrfz", "tpg_qrfz", "tni_qrfz", "tnr_qrfz", "tps_iaus", "tni_iaus", "tpi_ide", "t_Efrw", "t_Efsw"]
+
+
+def thompson_tables_save(path):
+    """every look-up table thompson_init built, to one .npz: a process that runs the oracle beside others (the ranks of a multi-process
+    test) loads them with thompson_init_from instead of integrating them again (10 s a process)"""
+    np.savez(path, **{n: thompson_table(n) for n in THOMPSON_TABLES})
+
+
+def thompson_init_from(params, flags, path):
+    """thompson_init without the table integration: the constants and size bins are made as always, the tables are copied from a file
+    thompson_tables_save wrote in a process that was initialised with the same params and flags"""
+    thompson_init(params, flags, build_tables=False)
+    fn = lib().orc_thompson_table
+    fn.restype = ctypes.POINTER(ctypes.c_double)
+    with np.load(path) as z:
+        assert sorted(z.files) == sorted(THOMPSON_TABLES)
+        for name in THOMPSON_TABLES:
+            a = np.ascontiguousarray(z[name], np.float64)
+            n = ctypes.c_size_t()
+            ptr = fn(name.encode(), ctypes.byref(n))
+            assert ptr and n.value == a.size, (name, n.value, a.size)
+            ctypes.memmove(ptr, a.ctypes.data, a.nbytes)
+
+
 TH_DIAG_N = 8
 
 
