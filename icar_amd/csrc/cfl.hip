@@ -22,23 +22,33 @@ k_max_courant(Dims d, const float *__restrict__ u, const float *__restrict__ v,
     const rsrc_t ru = mk(u), rv = mk(v), rw = mk(w);
     auto ld = [](rsrc_t r, int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0)); };
     float cur = 0.0f;
+    bool nan_wind = false;                                       // (a lane mask: scalar registers)
     if (i < d.nx) {
         const int vi = 4 * i, nxu = d.nx + 1;
         float wbelow = 0.0f;
 #pragma unroll 1
         for (int k = 0; k < d.nz; ++k) {
             const int sc = 4 * d.idx(0, k, j), scu = 4 * (nxu * (k + d.nz * j));     // wave-uniform
-            const float au = fmaxf(fabsf(ld(ru, vi, scu)), fabsf(ld(ru, vi, scu + 4)));
-            const float av = fmaxf(fabsf(ld(rv, vi, sc)), fabsf(ld(rv, vi, sc + 4 * d.sj)));
+            const float u0 = fabsf(ld(ru, vi, scu)), u1 = fabsf(ld(ru, vi, scu + 4));
+            const float v0 = fabsf(ld(rv, vi, sc)), v1 = fabsf(ld(rv, vi, sc + 4 * d.sj));
+            const float au = fmaxf(u0, u1);
+            const float av = fmaxf(v0, v1);
             const float aw0 = fabsf(ld(rw, vi, sc));
             const float aw = (k == 0) ? aw0 : fmaxf(aw0, wbelow);                     // (level 0 looks at itself, :281)
             const float cw = au / dx + av / dx + aw / dzl[k];
             cur = fmaxf(cur, cw);
             wbelow = aw0;
+            // fmaxf returns its other argument when one is NaN (as the reference's MAX does): a NaN wind would leave no trace in
+            // the maximum.  A sum of magnitudes is NaN exactly when one of them is (inf + inf is inf)
+            const float probe = (u0 + u1) + (v0 + v1) + aw0;
+            nan_wind |= probe != probe;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) cur = fmaxf(cur, __shfl_down(cur, o));
-    if (threadIdx.x == 0) atomicMax(out, __float_as_uint(cur));   // non-negative floats order like unsigned ints
+    // non-negative floats order like unsigned ints, and the quiet NaN lies above +inf: a column with a NaN wind makes the maximum NaN
+    // (compute_dt reports it)
+    unsigned b = nan_wind ? 0x7fc00000u : __float_as_uint(cur);
+    for (int o = 32; o > 0; o >>= 1) { const unsigned x = __shfl_down(b, o); b = x > b ? x : b; }
+    if (threadIdx.x == 0) atomicMax(out, b);
 }
 
 // out != nullptr: the maximum is copied to the host (one stream synchronisation).  d_out != nullptr: it is left in device

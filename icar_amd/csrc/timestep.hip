@@ -304,7 +304,8 @@ static int substep_open_early(icar_hip_ctx *c, bool maybe_last)
 // already applied the interior and strip microphysics of the abandoned sub-step and advanced mp_last_model_time: a caller that
 // retried would run the microphysics twice for one model time.  The reference STOPs where update_dt fails (time_step.f90:322-328);
 // here the context is marked failed and every later stepping call returns an error until the caller reloads the fields and
-// sets the model clock (icar_hip_model_time_set clears the mark: that is what a restart does).
+// sets the model clock (icar_hip_model_time_set clears the mark and starts the microphysics clock again at -999: that is what a
+// restart does).
 static int update_dt_opened(icar_hip_ctx *c, double *dt)
 {
     if (icar_update_dt(c, dt) == 0) return 0;
@@ -526,7 +527,16 @@ int icar_hip_step_configure(icar_hip_ctx *c, const icar_hip_step_config *cfg, co
     return 0;
 }
 
-int icar_hip_model_time_set(icar_hip_ctx *c, double seconds) { if (!c) { icar_set_error("model_time_set: null argument"); return 1; } c->step.model_time = seconds; c->step.failed = false; return 0; }
+int icar_hip_model_time_set(icar_hip_ctx *c, double seconds)
+{
+    if (!c) { icar_set_error("model_time_set: null argument"); return 1; }
+    c->step.model_time = seconds;
+    // clearing the mark is a restart: the abandoned opening left mp_last_model_time at the time of the failure, and a caller that sets
+    // that time again would run the microphysics over mp_dt = 0.  The reference restarts with last_model_time = -999 (mp_driver.f90:44).
+    // Without the mark the microphysics clock is left alone: a host that keeps the clock itself sets it after every sub-step.
+    if (c->step.failed) { c->step.failed = false; c->step.mp_last_model_time = -999.0; }
+    return 0;
+}
 double icar_hip_model_time(const icar_hip_ctx *c) { return c ? c->step.model_time : 0.0; }
 int icar_hip_mp_reset(icar_hip_ctx *c) { if (!c) { icar_set_error("mp_reset: null argument"); return 1; } c->step.mp_last_model_time = -999.0; return 0; }
 

@@ -672,7 +672,9 @@ int icar_hip_nsas_upload(icar_hip_ctx *ctx, int which, const void *host);
 int icar_hip_nsas_download(icar_hip_ctx *ctx, int which, void *host);
 
 /* ---- T2: CFL reduction for compute_dt (src/main/time_step.f90:217-330, cfl_strictness 3) -----
- * out = max over the tile of max(|u_i|,|u_i+1|)/dx + max(|v_j|,|v_j+1|)/dx + max(|w_k|,|w_k-1|)/dz_levels(k) */
+ * out = max over the tile of max(|u_i|,|u_i+1|)/dx + max(|v_j|,|v_j+1|)/dx + max(|w_k|,|w_k-1|)/dz_levels(k).
+ * A NaN among the winds a cell reads makes the result NaN (the reference's MAX would drop it and step on with a dt of the other
+ * cells): icar_hip_compute_dt / _update_dt / _step / _step_n then fail with "the CFL maximum is NaN (the winds contain NaN)". */
 int icar_hip_max_courant(icar_hip_ctx *ctx, float dx, const float *dz_levels, float *out);
 /* Same reduction, result left in DEVICE memory at d_out (one REAL(4) owned by the caller), no host synchronisation:
  * `call co_min(seconds)` (time_step.f90:413) becomes a 1-element all-reduce(max) of d_out over the images on the device
@@ -922,7 +924,13 @@ int icar_hip_co_max(icar_hip_ctx *ctx, double *value);
  *                           An error from icar_hip_step / icar_hip_step_n leaves the fields undefined (the reference STOPs
  *                           where update_dt fails, :322-328): when the failing sub-step had already been opened the context
  *                           is marked failed and every stepping entry point returns an error until the caller has reloaded
- *                           the fields and set the clock again (icar_hip_model_time_set).
+ *                           the fields and set the clock again (icar_hip_model_time_set).  Clearing the mark is a restart:
+ *                           icar_hip_model_time_set then also puts last_model_time of the microphysics back to -999, as
+ *                           icar_hip_mp_reset does, so that the next microphysics call is a first one (mp_dt = max(update_interval,
+ *                           dt)) and the context continues as a newly created one with the same fields and clock would.  On a
+ *                           context that is not marked failed icar_hip_model_time_set sets the clock and nothing else.  When
+ *                           update_dt fails with no sub-step opened the context is not marked: its fields and clock are those
+ *                           after the last completed sub-step (diagnostics aside, see below), and stepping may go on.
  *                           The DIAGNOSTIC fields (temperature, density, pressure_interface, surface_pressure,
  *                           temperature_interface, u_mass, v_mass, w_real) after icar_hip_step / icar_hip_step_n are those of
  *                           the call's LAST sub-step -- what the reference leaves, too; the sub-steps before it write only the

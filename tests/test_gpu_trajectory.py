@@ -227,34 +227,11 @@ def test_whole_step_loop_exact_mode_equals_cpu_chain(th_oracle, oracle):
     dt0 = min(float(f32(0.9) / f32(oracle.max_courant(c["u"], c["v"], c["w"], c["dz_levels"], float(c["dx"])))), 120.0)
     end = 6.4 * dt0                                           # ~7 sub-steps, the last one shortened
     n_dev = step(d, end, opt, forced=forced, diagnostics=True)
-    # ---- the same loop on the CPU ----
-    s = {k: c[k].copy() for k in ADV_ORDER + ["u", "v", "w", "pressure"]}
-    acc = np.zeros((ny, nx), np.float64)
+    # ---- the same loop on the CPU (tests/step_loop_model.py) ----
+    import step_loop_model
     th_oracle.set_math_mode(0); oracle.set_math_mode(0)
-    t, n_cpu, dts, t_mp = 0.0, 0, [], None
-    while t < end:                                                                                      # :462
-        dt = min(float(f32(0.9) / f32(oracle.max_courant(s["u"], s["v"], s["w"], c["dz_levels"], float(c["dx"])))), 120.0)   # :465, :417
-        if t + dt > end: dt = end - t                                                                   # :469-471
-        enforce = (end - t) < dt * 2
-        dt4 = float(f32(dt))
-        diag = oracle.diagnostic_update(s["pressure"], s["potential_temperature"], s["u"], s["v"], s["w"], c["dzdx"], c["dzdy"], c["jacobian"])   # :474
-        z = [np.zeros((ny, nx), np.float32) for _ in range(5)]
-        # mp_driver.f90:698-713: the microphysics integrates over the time since ITS last call (= the previous sub-step's dt), the
-        # first call over this sub-step's
-        mp_dt = dt4 if t_mp is None else float(f32(t - t_mp)); t_mp = t
-        th_oracle.thompson(s["water_vapor"], s["cloud_water"], s["rain"], s["cloud_ice"], s["snow"], s["graupel"], s["ice_number"],
-                           s["rain_number"], s["potential_temperature"], diag["exner"], s["pressure"], c["dz_mass"], mp_dt, *z,
-                           1, nx, 1, ny, 1, nz, 2, nx - 1, 2, ny - 1, 1, nz)                             # :512-523
-        acc += z[0]
-        q = np.stack([s[n] for n in ADV_ORDER]).copy()
-        oracle.advect(2, q, s["u"], s["v"], s["w"], diag["density"], c["jacobian"], c["jacobian_u"], c["jacobian_v"], c["jacobian_w"],
-                      c["advection_dz"], c["dz_levels"], float(c["dx"]), dt4)                            # :529
-        for m, n in enumerate(ADV_ORDER): s[n] = q[m].copy()
-        for n, fb in forced:                                                                            # :534
-            oracle.apply_forcing(s[n], dq[n], dt, int(fb), 1, 1, 1, 1)
-        if enforce:
-            for n in ADV_ORDER: oracle.enforce_limits(s[n])
-        t += dt; n_cpu += 1; dts.append(dt)
+    r = step_loop_model.run(th_oracle, c, dq, forced=forced, scheme="thompson", advection=kADV_MPDATA, end=end)
+    s, acc, diag, t, n_cpu, dts = r.s, r.acc, r.diag, r.t, r.n, r.dts
     assert n_dev == n_cpu and n_cpu >= 6, (n_dev, n_cpu)
     assert all(np.isfinite(a).all() for a in s.values()) and float(s["potential_temperature"].max()) < 600.0, "the case must stay physical"
     assert abs(d.model_time_seconds - t) == 0.0 or abs(d.model_time_seconds - end) < 1e-9
