@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libicar_hip.so")
-SOURCES = ["capi.hip", "halo_pack.hip", "cfl.hip", "advect.hip", "mpdata.hip", "mpdata_exact.hip", "mp_simple.hip", "pbl_simple.hip", "pbl_ysu.hip", "ra_simple.hip", "sfc_basic.hip", "lsm_noah.hip", "lsm_noah_driver.hip", "cu_bmj.hip", "cu_tiedtke.hip", "cu_nsas.hip", "mp_thompson.hip", "thompson_tables.hip", "step.hip", "linear_winds.hip", "forcing.hip", "iterative_winds.hip", "mp_wsm3.hip", "mp_wsm6.hip", "comm.hip", "timestep.hip"]
+SOURCES = ["capi.hip", "halo_pack.hip", "cfl.hip", "advect.hip", "mpdata.hip", "mpdata_exact.hip", "mp_simple.hip", "pbl_simple.hip", "pbl_ysu.hip", "ra_simple.hip", "sfc_basic.hip", "lsm_noah.hip", "lsm_noah_driver.hip", "cu_bmj.hip", "cu_tiedtke.hip", "cu_nsas.hip", "mp_thompson.hip", "thompson_tables.hip", "step.hip", "linear_winds.hip", "forcing.hip", "forcing2d.hip", "iterative_winds.hip", "mp_wsm3.hip", "mp_wsm6.hip", "comm.hip", "timestep.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # finite data only: drop the NaN-canonicalisation v_max x,x,x in front of every fmin/fmax (no effect on finite results)
 PER_FILE_FLAGS = {"advect.hip": ["-fno-honor-nans"],

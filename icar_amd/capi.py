@@ -41,7 +41,14 @@ SYMBOLS = [
     "icar_hip_convection_init", "icar_hip_cu_nsas", "icar_hip_nsas_upload", "icar_hip_nsas_download",
     "icar_hip_forcing_configure", "icar_hip_forcing_upload", "icar_hip_forcing_download", "icar_hip_interpolate_forcing",
     "icar_hip_update_delta_fields", "icar_hip_forcing_step",
+    "icar_hip_forcing2d_upload", "icar_hip_forcing2d_download", "icar_hip_interpolate_forcing_2d", "icar_hip_update_delta_fields_2d",
+    "icar_hip_apply_forcing_2d", "icar_hip_forcing2d_enable", "icar_hip_forcing2d_get", "icar_hip_forcing2d_set",
 ]
+
+# enum icar_hip_forced2d (include/icar_hip.h): the 2-D variables the reference forces, and what icar_hip_forcing2d_get / _set address
+FORCED2D = {"sst": 0, "shortwave": 1, "longwave": 2, "external_precipitation": 3}
+FORCED2D_N = 4
+FORCED2D_DATA, FORCED2D_DQDT = 0, 1
 
 
 class lt_options_c(ctypes.Structure):          # struct icar_hip_lt_options (include/icar_hip.h)
@@ -184,6 +191,14 @@ def lib():
         L.icar_hip_interpolate_forcing.argtypes = [vp, ctypes.POINTER(ci), ci, ci, ci, ci]
         L.icar_hip_update_delta_fields.argtypes = [vp, ctypes.POINTER(ci), ci, cd]
         L.icar_hip_forcing_step.argtypes = [vp, ctypes.POINTER(ci), ci, ci, ci, ci, ci, cf, ci, cd]
+        L.icar_hip_forcing2d_upload.argtypes = [vp, ci, vp, ci, ci]
+        L.icar_hip_forcing2d_download.argtypes = [vp, ci, vp, ctypes.c_size_t]
+        L.icar_hip_interpolate_forcing_2d.argtypes = [vp, ctypes.POINTER(ci), ci, ci]
+        L.icar_hip_update_delta_fields_2d.argtypes = [vp, ctypes.POINTER(ci), ci, cd]
+        L.icar_hip_apply_forcing_2d.argtypes = [vp, cd]
+        L.icar_hip_forcing2d_enable.argtypes = [vp, ctypes.POINTER(ci), ci]
+        L.icar_hip_forcing2d_get.argtypes = [vp, ci, ci, vp]
+        L.icar_hip_forcing2d_set.argtypes = [vp, ci, ci, vp]
         _lib = L
     return _lib
 

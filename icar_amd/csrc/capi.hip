@@ -160,6 +160,7 @@ int icar_hip_ctx_destroy(icar_hip_ctx *c)
     icar_thompson_free(c);
     icar_linwinds_free(c);
     icar_forcing_free(c);
+    icar_forcing2d_free(c);
     icar_comm_free(c);
     if (c->step.h_val) hipHostFree(c->step.h_val);
     if (c->on_aux) c->stream = c->main_saved;

@@ -29,6 +29,7 @@ struct IcarComm;         // comm.hip
 struct CuState;          // cu_bmj.hip
 struct YsuState;         // pbl_ysu.hip
 struct ForcingState;     // forcing.hip
+struct Forcing2dState;   // forcing2d.hip
 struct NoahState;        // lsm_noah.hip
 struct LsmDriverState;   // lsm_noah_driver.hip
 
@@ -126,6 +127,7 @@ struct icar_hip_ctx {
     Wsm6State *wsm6 = nullptr;
     IcarComm *comm = nullptr;            // halo transport + co_min (comm.hip)
     ForcingState *forcing = nullptr;     // forcing.hip: the look-up tables, the forcing's own arrays, the temporaries of interpolate_forcing
+    Forcing2dState *forcing2d = nullptr; // forcing2d.hip: the forced 2-D variables' forcing arrays, dqdt_2d, external_precipitation, the enabled set
     IcarStepState step;                  // timestep.hip
     // timing
     bool timing = false;
@@ -279,3 +281,11 @@ __global__ void k_lw_colsmooth(Dims d, int w, const double *__restrict__ rowmean
 void icar_forcing_free(icar_hip_ctx *c);
 int icar_interpolate_forcing_run(icar_hip_ctx *c, const int *fields, int n, int pressure_field, int theta_field, int update);
 int icar_update_delta_fields_run(icar_hip_ctx *c, const int *fields, int n, double dt);
+// ... the mass grid's geolut as forcing_configure stored it (false: not configured), for forcing2d.hip
+struct IcarGeo2d { const int4 *x, *y; const float4 *w; int nx, ny, nx_f, ny_f; };
+bool icar_forcing_mass_geo(const icar_hip_ctx *c, IcarGeo2d *g);
+// forcing2d.hip
+void icar_forcing2d_free(icar_hip_ctx *c);
+int icar_forcing2d_apply_run(icar_hip_ctx *c, double dt);                   // apply_forcing's 2-D statements for the enabled set (nothing enabled: no launch)
+int icar_forcing2d_step_check(icar_hip_ctx *c, const char *who, double dt); // forcing_step: what the enabled set would be refused for
+int icar_forcing2d_step_run(icar_hip_ctx *c, double dt);                    // forcing_step: geo_interp2d (update) and the 2-D delta of the enabled set

@@ -166,6 +166,14 @@ static int geo_store(icar_hip_ctx *c, FGeoDev &d, const icar_hip_forcing_geo *g,
     return 0;
 }
 
+bool icar_forcing_mass_geo(const icar_hip_ctx *c, IcarGeo2d *g)
+{
+    const ForcingState *s = c->forcing;
+    if (!s || !s->configured || !s->mass.set) return false;
+    *g = IcarGeo2d{s->mass.x, s->mass.y, s->mass.w, s->mass.nx, s->mass.ny, s->mass.nx_f, s->mass.ny_f};
+    return true;
+}
+
 static FGeoArg geo_arg(const FGeoDev &d) { return FGeoArg{d.x, d.y, d.w, d.vz, d.vw, d.nx, d.ny, d.nx_f, d.nz_f}; }
 
 static int forcing_configure_run(icar_hip_ctx *c, const icar_hip_forcing_geo *mass, const icar_hip_forcing_geo *u, const icar_hip_forcing_geo *v,
@@ -436,10 +444,12 @@ int icar_hip_forcing_step(icar_hip_ctx *c, const int *fields, int nfields, int p
         const int f = m < nfields ? fields[m] : ICAR_F_W;
         if (!c->field[f]) return refuse(who, "update_delta_fields needs field %ld on the device: it has not been uploaded", f);
     }
+    if (icar_forcing2d_step_check(c, who, dt_seconds)) return 1;                                                   // the enabled 2-D variables (forcing2d.hip)
     for (int m = 0; m <= nfields; ++m) if (!destination(c, m < nfields ? fields[m] : ICAR_F_W, 1)) return 1;      // the mirrors, w's included
     if (icar_interpolate_forcing_run(c, fields, nfields, pressure_field, theta_field, 1)) return 1;
     if (icar_hip_update_winds(c, windtype, wind_iterations, dx, halo, 1)) return 1;
-    return icar_update_delta_fields_run(c, fields, nfields, dt_seconds);
+    if (icar_update_delta_fields_run(c, fields, nfields, dt_seconds)) return 1;
+    return icar_forcing2d_step_run(c, dt_seconds);
 }
 
 }  // extern "C"

@@ -455,6 +455,7 @@ int icar_substep(icar_hip_ctx *c, double dt, bool enforce, bool last)
     for (int m = 0; m < nr; ++m) scalars_only = scalars_only && rest_f[m] >= 0 && rest_f[m] < ICAR_N_ADVECTABLE;
     if (beside && !scalars_only && icar_hip_aux_join(c)) return 1;
     if (nr && icar_apply_forcing_run(c, dt, rest_f, rest_b, nr, g.west_boundary, g.east_boundary, g.south_boundary, g.north_boundary)) return 1;   // :534
+    if (icar_forcing2d_apply_run(c, dt)) return 1;                                // :534 the forced 2-D variables (domain_obj.f90:2400-2402, :2438-2445), once icar_hip_forcing2d_enable listed some
     if (enforce && icar_enforce_limits_run(c, g.advect_fields, g.n_advect)) return 1;                                                                // :537-539
     if (beside && scalars_only && icar_hip_aux_join(c)) return 1;
     return 0;

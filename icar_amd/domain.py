@@ -210,6 +210,22 @@ class domain_t:
         from .forcing import update_delta_fields
         update_delta_fields(self, dt_seconds, names)
 
+    def interpolate_forcing_2d(self, names, update=False):
+        """the two_d branch of domain%interpolate_forcing (domain_obj.f90:2595-2600, geo_interp2d) for sst / shortwave / longwave /
+        external_precipitation (icar_amd.forcing)."""
+        from .forcing import interpolate_forcing_2d
+        interpolate_forcing_2d(self, names, update)
+
+    def update_delta_fields_2d(self, names, dt_seconds):
+        """domain%update_delta_fields(dt) for 2-D variables (domain_obj.f90:2355-2356)."""
+        from .forcing import update_delta_fields_2d
+        update_delta_fields_2d(self, names, dt_seconds)
+
+    def apply_forcing_2d(self, dt_seconds):
+        """domain%apply_forcing(dt) for the enabled 2-D variables and the precipitation sum (domain_obj.f90:2400-2402, :2438-2445)."""
+        from .forcing import apply_forcing_2d
+        apply_forcing_2d(self, dt_seconds)
+
     def enforce_limits(self, names):
         """domain%enforce_limits (domain_obj.f90:2228-2243): clamp negatives to zero."""
         ids = (ctypes.c_int * len(names))(*[self.fid(n) for n in names])

@@ -7,7 +7,7 @@ import ctypes
 
 import numpy as np
 
-from .capi import lib, check, forcing_geo_c
+from .capi import lib, check, forcing_geo_c, FORCED2D, FORCED2D_DATA, FORCED2D_DQDT
 
 
 class geo_t:
@@ -109,8 +109,14 @@ def update_delta_fields(domain, dt_seconds, names=None):
     check(lib().icar_hip_update_delta_fields(domain.ctx, ids, n, ctypes.c_double(dt_seconds)), "icar_hip_update_delta_fields")
 
 
-def forcing_step(domain, forcing, options, dt_seconds, pressure="pressure", theta="potential_temperature", upload=True):
-    """driver.f90:133-137 behind boundary%update_forcing: interpolate_forcing(update = .true.), update_winds, update_delta_fields"""
+def forcing_step(domain, forcing, options, dt_seconds, pressure="pressure", theta="potential_temperature", upload=True, forced_2d=None):
+    """driver.f90:133-137 behind boundary%update_forcing: interpolate_forcing(update = .true.), update_winds, update_delta_fields.
+    forced_2d = {name: array (ny_f, nx_f)}: these 2-D variables are uploaded and enabled first (forcing2d_enable), so the same call
+    interpolates them and takes their delta, and every later sub-step applies them; None leaves the enabled set as it is"""
+    if forced_2d is not None:
+        for n, a in forced_2d.items():
+            forcing2d_upload(domain, n, a)
+        forcing2d_enable(domain, list(forced_2d))
     names = list(forcing.variables)
     if upload:
         for n in names:
@@ -122,3 +128,63 @@ def forcing_step(domain, forcing, options, dt_seconds, pressure="pressure", thet
     check(lib().icar_hip_forcing_step(domain.ctx, ids, n, pf, tf, int(options.physics.windtype), int(p.wind_iterations), ctypes.c_float(domain.dx),
                                       halo, ctypes.c_double(dt_seconds)), "icar_hip_forcing_step")
     domain._forced_names = names
+
+
+# ---- the 2-D forced variables (include/icar_hip.h, F3): sst, shortwave, longwave, external_precipitation ----------------------------
+def _which(names):
+    ids = [n if isinstance(n, int) else FORCED2D[n] for n in names]
+    return (ctypes.c_int * max(len(ids), 1))(*ids), len(ids)
+
+
+def _one(name):
+    return name if isinstance(name, int) else FORCED2D[name]
+
+
+def forcing2d_upload(domain, name, array):
+    """input_data%data_2d of a 2-D forcing variable, (ny_f, nx_f), as just read"""
+    a = np.ascontiguousarray(array, np.float32)
+    if a.ndim != 2:
+        raise ValueError(f"{name}: a 2-D forcing variable is (ny_f, nx_f)")
+    check(lib().icar_hip_forcing2d_upload(domain.ctx, _one(name), a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0]), f"icar_hip_forcing2d_upload {name}")
+
+
+def forcing2d_download(domain, name, shape):
+    a = np.empty(shape, np.float32)
+    check(lib().icar_hip_forcing2d_download(domain.ctx, _one(name), a.ctypes.data_as(ctypes.c_void_p), a.size), f"icar_hip_forcing2d_download {name}")
+    return a
+
+
+def interpolate_forcing_2d(domain, names, update=False):
+    """the two_d branch of domain%interpolate_forcing (domain_obj.f90:2595-2600): geo_interp2d into dqdt_2d when update, else data_2d"""
+    ids, n = _which(names)
+    check(lib().icar_hip_interpolate_forcing_2d(domain.ctx, ids, n, int(bool(update))), "icar_hip_interpolate_forcing_2d")
+
+
+def update_delta_fields_2d(domain, names, dt_seconds):
+    """domain_obj.f90:2355-2356 for the listed 2-D variables"""
+    ids, n = _which(names)
+    check(lib().icar_hip_update_delta_fields_2d(domain.ctx, ids, n, ctypes.c_double(dt_seconds)), "icar_hip_update_delta_fields_2d")
+
+
+def apply_forcing_2d(domain, dt_seconds):
+    """domain_obj.f90:2400-2402 and :2438-2445 for the enabled set"""
+    check(lib().icar_hip_apply_forcing_2d(domain.ctx, ctypes.c_double(dt_seconds)), "icar_hip_apply_forcing_2d")
+
+
+def forcing2d_enable(domain, names):
+    """the 2-D variables forcing_step and every sub-step handle from now on; an empty list disables"""
+    ids, n = _which(names)
+    check(lib().icar_hip_forcing2d_enable(domain.ctx, ids, n), "icar_hip_forcing2d_enable")
+
+
+def forcing2d_get(domain, name, dqdt=False):
+    a = np.empty((domain.ny, domain.nx), np.float32)
+    check(lib().icar_hip_forcing2d_get(domain.ctx, _one(name), FORCED2D_DQDT if dqdt else FORCED2D_DATA, a.ctypes.data_as(ctypes.c_void_p)), f"icar_hip_forcing2d_get {name}")
+    return a
+
+
+def forcing2d_set(domain, name, array, dqdt=False):
+    a = np.ascontiguousarray(array, np.float32)
+    if a.shape != (domain.ny, domain.nx):
+        raise ValueError(f"{name}: data_2d and dqdt_2d are (ny, nx)")
+    check(lib().icar_hip_forcing2d_set(domain.ctx, _one(name), FORCED2D_DQDT if dqdt else FORCED2D_DATA, a.ctypes.data_as(ctypes.c_void_p)), f"icar_hip_forcing2d_set {name}")

@@ -44,6 +44,9 @@ module icar_hip
             ICAR_TIEDTKE_TEND_QC, ICAR_TIEDTKE_TEND_QI, ICAR_TIEDTKE_PRATEC, ICAR_TIEDTKE_KTYPE, ICAR_TIEDTKE_N, &
             hip_convection_init, hip_cu_nsas, hip_nsas_upload, hip_nsas_download, ICAR_CU_NSAS, &
             hip_forcing_geo_t, hip_forcing_configure, hip_forcing_upload, hip_interpolate_forcing, hip_update_delta_fields, hip_forcing_step, &
+            hip_forcing2d_upload, hip_forcing2d_download, hip_forcing2d_interpolate, hip_forcing2d_update_delta, hip_forcing2d_apply, &
+            hip_forcing2d_enable, hip_forcing2d_get, hip_forcing2d_set, ICAR_FORCED2D_SST, ICAR_FORCED2D_SHORTWAVE, ICAR_FORCED2D_LONGWAVE, &
+            ICAR_FORCED2D_EXTERNAL_PRECIPITATION, ICAR_FORCED2D_N, ICAR_FORCED2D_DATA, ICAR_FORCED2D_DQDT, &
             ICAR_NSAS_TEND_QC, ICAR_NSAS_TEND_QI, ICAR_NSAS_PRATEC, ICAR_NSAS_HBOT, ICAR_NSAS_HTOP, ICAR_NSAS_HPBL, ICAR_NSAS_N, &
             ICAR_CU_CLDEFI, ICAR_CU_ACC_CONV_PCP, ICAR_CU_RAINCV, ICAR_CU_CUTOP, ICAR_CU_CUBOT, ICAR_CU_TEND_TH, ICAR_CU_TEND_QV, ICAR_CU_N, &
             ICAR_NEIGHBOR_NONE, ICAR_NEIGHBOR_SELF, ICAR_N_ADVECTABLE
@@ -121,6 +124,10 @@ module icar_hip
   ! enum icar_hip_tiedtke_array: the Tiedtke scheme's own arrays: tend%qc, tend%qi (nx,nz,ny), PRATEC (nx,ny) REAL(4), KTYPE (nx,ny) INTEGER(4)
   integer(c_int), parameter :: ICAR_TIEDTKE_TEND_QC=0, ICAR_TIEDTKE_TEND_QI=1, ICAR_TIEDTKE_PRATEC=2, ICAR_TIEDTKE_KTYPE=3, ICAR_TIEDTKE_N=4
   integer(c_int), parameter :: ICAR_CU_NSAS = 4         ! kCU_NSAS, icar_constants.f90
+  ! enum icar_hip_forced2d (include/icar_hip.h): the 2-D variables the reference forces, and what hip_forcing2d_get / _set address
+  integer(c_int), parameter :: ICAR_FORCED2D_SST = 0, ICAR_FORCED2D_SHORTWAVE = 1, ICAR_FORCED2D_LONGWAVE = 2, &
+                               ICAR_FORCED2D_EXTERNAL_PRECIPITATION = 3, ICAR_FORCED2D_N = 4
+  integer(c_int), parameter :: ICAR_FORCED2D_DATA = 0, ICAR_FORCED2D_DQDT = 1
   ! enum icar_hip_nsas_array: the NSAS scheme's own REAL(4) arrays: tend%qc, tend%qi (nx,nz,ny), PRATEC, HBOT, HTOP, hpbl (nx,ny)
   integer(c_int), parameter :: ICAR_NSAS_TEND_QC=0, ICAR_NSAS_TEND_QI=1, ICAR_NSAS_PRATEC=2, ICAR_NSAS_HBOT=3, ICAR_NSAS_HTOP=4, ICAR_NSAS_HPBL=5, &
                                ICAR_NSAS_N=6
@@ -498,6 +505,30 @@ module icar_hip
                                                    bind(C, name="icar_hip_forcing_step")
        import; type(c_ptr), value :: ctx; integer(c_int), value :: n, pressure_field, theta_field, windtype, wind_iterations, halo
        integer(c_int), intent(in) :: fields(*); real(c_float), value :: dx; real(c_double), value :: dt_seconds
+     end function
+     integer(c_int) function icar_hip_forcing2d_upload(ctx, which, lo, nx_f, ny_f) bind(C, name="icar_hip_forcing2d_upload")
+       import; type(c_ptr), value :: ctx, lo; integer(c_int), value :: which, nx_f, ny_f
+     end function
+     integer(c_int) function icar_hip_forcing2d_download(ctx, which, lo, count) bind(C, name="icar_hip_forcing2d_download")
+       import; type(c_ptr), value :: ctx, lo; integer(c_int), value :: which; integer(c_size_t), value :: count
+     end function
+     integer(c_int) function icar_hip_interpolate_forcing_2d(ctx, which, n, update) bind(C, name="icar_hip_interpolate_forcing_2d")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: n, update; integer(c_int), intent(in) :: which(*)
+     end function
+     integer(c_int) function icar_hip_update_delta_fields_2d(ctx, which, n, dt_seconds) bind(C, name="icar_hip_update_delta_fields_2d")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: n; integer(c_int), intent(in) :: which(*); real(c_double), value :: dt_seconds
+     end function
+     integer(c_int) function icar_hip_apply_forcing_2d(ctx, dt_seconds) bind(C, name="icar_hip_apply_forcing_2d")
+       import; type(c_ptr), value :: ctx; real(c_double), value :: dt_seconds
+     end function
+     integer(c_int) function icar_hip_forcing2d_enable(ctx, which, n) bind(C, name="icar_hip_forcing2d_enable")
+       import; type(c_ptr), value :: ctx; integer(c_int), value :: n; integer(c_int), intent(in) :: which(*)
+     end function
+     integer(c_int) function icar_hip_forcing2d_get(ctx, which, what, host) bind(C, name="icar_hip_forcing2d_get")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which, what
+     end function
+     integer(c_int) function icar_hip_forcing2d_set(ctx, which, what, host) bind(C, name="icar_hip_forcing2d_set")
+       import; type(c_ptr), value :: ctx, host; integer(c_int), value :: which, what
      end function
      integer(c_int) function icar_hip_update_winds(ctx, windtype, wind_iterations, dx, halo, update) bind(C, name="icar_hip_update_winds")
        import; type(c_ptr), value :: ctx; integer(c_int), value :: windtype, wind_iterations, halo, update; real(c_float), value :: dx
@@ -1391,6 +1422,66 @@ contains
     double precision, intent(in) :: dt_seconds
     call check(icar_hip_forcing_step(ctx%p, fields, int(size(fields),c_int), pressure_field, theta_field, int(windtype,c_int), &
                int(wind_iterations,c_int), real(dx,c_float), int(halo,c_int), real(dt_seconds,c_double)), "forcing_step")
+  end subroutine
+
+  !> input_data%data_2d of a forced 2-D variable (ICAR_FORCED2D_*), as boundary%update_forcing has just read it
+  subroutine hip_forcing2d_upload(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(in), target, contiguous :: a(:,:)
+    call check(icar_hip_forcing2d_upload(ctx%p, which, c_loc(a), int(size(a,1),c_int), int(size(a,2),c_int)), "forcing2d_upload")
+  end subroutine
+
+  subroutine hip_forcing2d_download(ctx, which, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which
+    real(c_float), intent(inout), target, contiguous :: a(:,:)
+    call check(icar_hip_forcing2d_download(ctx%p, which, c_loc(a), int(size(a),c_size_t)), "forcing2d_download")
+  end subroutine
+
+  !> the two_d branch of domain%interpolate_forcing (domain_obj.f90:2595-2600): geo_interp2d into dqdt_2d (update) or data_2d
+  subroutine hip_forcing2d_interpolate(ctx, which, update)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which(:)
+    logical, intent(in) :: update
+    call check(icar_hip_interpolate_forcing_2d(ctx%p, which, int(size(which),c_int), merge(1_c_int, 0_c_int, update)), "interpolate_forcing_2d")
+  end subroutine
+
+  !> domain%update_delta_fields(dt) for 2-D variables (domain_obj.f90:2355-2356)
+  subroutine hip_forcing2d_update_delta(ctx, which, dt_seconds)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which(:)
+    double precision, intent(in) :: dt_seconds
+    call check(icar_hip_update_delta_fields_2d(ctx%p, which, int(size(which),c_int), real(dt_seconds,c_double)), "update_delta_fields_2d")
+  end subroutine
+
+  !> domain%apply_forcing(dt) for the enabled 2-D variables and the precipitation sum (domain_obj.f90:2400-2402, :2438-2445)
+  subroutine hip_forcing2d_apply(ctx, dt_seconds)
+    type(hip_ctx_t), intent(in) :: ctx
+    double precision, intent(in) :: dt_seconds
+    call check(icar_hip_apply_forcing_2d(ctx%p, real(dt_seconds,c_double)), "apply_forcing_2d")
+  end subroutine
+
+  !> the 2-D variables hip_forcing_step and every sub-step handle from now on; a zero-sized list disables
+  subroutine hip_forcing2d_enable(ctx, which)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which(:)
+    call check(icar_hip_forcing2d_enable(ctx%p, which, int(size(which),c_int)), "forcing2d_enable")
+  end subroutine
+
+  !> data_2d (ICAR_FORCED2D_DATA) or dqdt_2d (ICAR_FORCED2D_DQDT) of one forced 2-D variable, (nx, ny): restart files
+  subroutine hip_forcing2d_get(ctx, which, what, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which, what
+    real(c_float), intent(inout), target, contiguous :: a(:,:)
+    call check(icar_hip_forcing2d_get(ctx%p, which, what, c_loc(a)), "forcing2d_get")
+  end subroutine
+
+  subroutine hip_forcing2d_set(ctx, which, what, a)
+    type(hip_ctx_t), intent(in) :: ctx
+    integer(c_int), intent(in) :: which, what
+    real(c_float), intent(in), target, contiguous :: a(:,:)
+    call check(icar_hip_forcing2d_set(ctx%p, which, what, c_loc(a)), "forcing2d_set")
   end subroutine
 
   !> variable%meta_data%dqdt_3d -> device (the forcing tendency apply_forcing adds)

@@ -850,6 +850,47 @@ int icar_hip_update_delta_fields(icar_hip_ctx *ctx, const int *fields, int nfiel
 int icar_hip_forcing_step(icar_hip_ctx *ctx, const int *fields, int nfields, int pressure_field, int theta_field, int windtype,
                           int wind_iterations, float dx, int halo, double dt_seconds);
 
+/* ---- F3: the 2-D forced variables (variables_to_force, src/objects/domain_obj.f90:199, :212, :215, :272) -----------------------------
+ * sst, shortwave, longwave and external_precipitation through the same three places as the 3-D ones.  data_2d of the first three is the
+ * field slot (ICAR_F_SST, ICAR_F_SHORTWAVE, ICAR_F_LONGWAVE); external_precipitation%data_2d has no slot and is owned by the forcing
+ * state.  A context that never calls these issues exactly what it issued before; the 3-D entry points above keep refusing 2-D fields.
+ * All of them need icar_hip_forcing_configure first (the mass grid's geolut is the one geo_interp2d reads), _get / _set excepted.
+ * icar_hip_forcing2d_upload: input_data%data_2d (nx_f, ny_f) of the forcing variable as just read; the extents must be those of the
+ *     mass tables given to icar_hip_forcing_configure.  _download reads it back.
+ * icar_hip_interpolate_forcing_2d == the two_d branch of domain%interpolate_forcing (domain_obj.f90:2595-2600): geo_interp2d
+ *     (src/utilities/geo_reader.f90:1142-1182) over the whole memory ims:ime, jms:jme, all listed variables in one launch; update != 0
+ *     writes dqdt_2d (created if needed), update == 0 data_2d.
+ * icar_hip_update_delta_fields_2d == domain_obj.f90:2355-2356: dqdt_2d = (dqdt_2d - data_2d) / dt%seconds(), the difference in REAL(4),
+ *     the quotient in REAL(8), rounded once.
+ * icar_hip_apply_forcing_2d == domain_obj.f90:2400-2402 for the enabled set, data_2d = data_2d + (dqdt_2d * dt%seconds()) in REAL(8)
+ *     rounded once, and :2438-2445: accumulated_precipitation%data_2dd (ICAR_F_PRECIPITATION) takes external_precipitation * dt.  One
+ *     launch.  As the reference's `associated` tests do, it passes over an enabled variable whose data_2d or dqdt_2d is not on the device
+ *     and over the sum while ICAR_F_PRECIPITATION is not on the device (or external_precipitation is not enabled): neither is an error.
+ * icar_hip_forcing2d_enable: the variables icar_hip_forcing_step also interpolates (update) and takes the delta of, and that
+ *     icar_hip_substep / _step / _step_n apply at src/main/time_step.f90:534 on the main stream behind the 3-D forcing with the
+ *     sub-step's own dt.  n = 0 disables.
+ * icar_hip_forcing2d_get / _set: data_2d (ICAR_FORCED2D_DATA) or dqdt_2d (ICAR_FORCED2D_DQDT) of one variable, (nx, ny) REAL(4): for a
+ *     restart and for tests (external_precipitation has no field slot to go through).  _set creates the array.
+ * Refused before any launch, with a text that names the cause and the state left as it was: a call before forcing_configure, a bad id, a
+ * variable listed twice, a variable without uploaded data, data of other extents than the tables, dt not a positive finite number, a
+ * delta for a variable that has no dqdt_2d (or no data_2d).  Bit-identical to the compiled reference. */
+typedef enum icar_hip_forced2d {
+    ICAR_FORCED2D_SST = 0,                     /* domain%sst                      data_2d = ICAR_F_SST       */
+    ICAR_FORCED2D_SHORTWAVE = 1,               /* domain%shortwave                data_2d = ICAR_F_SHORTWAVE */
+    ICAR_FORCED2D_LONGWAVE = 2,                /* domain%longwave                 data_2d = ICAR_F_LONGWAVE  */
+    ICAR_FORCED2D_EXTERNAL_PRECIPITATION = 3,  /* domain%external_precipitation   owned by the forcing state */
+    ICAR_FORCED2D_N = 4
+} icar_hip_forced2d;
+enum { ICAR_FORCED2D_DATA = 0, ICAR_FORCED2D_DQDT = 1 };
+int icar_hip_forcing2d_upload(icar_hip_ctx *ctx, int which, const float *lo, int nx_f, int ny_f);
+int icar_hip_forcing2d_download(icar_hip_ctx *ctx, int which, float *lo, size_t count);
+int icar_hip_interpolate_forcing_2d(icar_hip_ctx *ctx, const int *which, int n, int update);
+int icar_hip_update_delta_fields_2d(icar_hip_ctx *ctx, const int *which, int n, double dt_seconds);
+int icar_hip_apply_forcing_2d(icar_hip_ctx *ctx, double dt_seconds);
+int icar_hip_forcing2d_enable(icar_hip_ctx *ctx, const int *which, int n);
+int icar_hip_forcing2d_get(icar_hip_ctx *ctx, int which, int what, float *host);
+int icar_hip_forcing2d_set(icar_hip_ctx *ctx, int which, int what, const float *host);
+
 /* ---- H1: halo faces (src/objects/exchangeable_obj.f90:138-356) --------------------------------
  * dir: 0=north 1=south 2=east 3=west.  pack gathers what exchangeable%put_<dir> would PUT
  * (my interior planes next to that edge, width halo, N/S over the full memory width so corners
